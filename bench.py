@@ -7,10 +7,14 @@ BASELINE config 2 -- 1 Mi values x 4 KiB, resident in HBM when timing starts.
 With N > 1 ranks each GPU builds its own table (one run per GPU, as in
 lsmtree compaction) and the 20-byte roots are all-gathered over RCCL every step.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...
 
-Rank 0 prints one JSON line (see DESIGN.md "Measurement").
+Rank 0 prints one JSON line (see DESIGN.md "Measurement").  A plain run sets up,
+warms up, times the K steps and prints the line; --full adds everything else the
+line can carry (the check against the oracle roots, the CPU baseline, the
+sub-configs and the C-ABI group in child processes, the kernels timed in runs of
+their own).  --dump-outputs DIR writes what the last timed step computed.
 """
 from __future__ import annotations
 
@@ -144,6 +148,16 @@ def parse(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: every rank's root checked against the committed "
+                         "oracle roots, the CPU baseline, the sub-config and C-ABI group children, the BFS image "
+                         "kernel (and, with --no-kernel-timing, the kernel split) timed in runs of their own; "
+                         "without it the run sets up, warms up, times --steps steps and prints its line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float32 / "
+                         "float64, under 64 MB in all): every table's root, a fixed seeded sample of its node "
+                         "rows with their indices, and the records configs' error words; the inputs are the same "
+                         "in every run with the same arguments")
     ap.add_argument("--config", choices=["sstable4k", "mixed", "records", "records_verify", "one_tree", "runs4",
                                          "api_flush", "small_flush"],
                     default="sstable4k",
@@ -190,9 +204,10 @@ def parse(argv=None):
     ap.add_argument("--value-bytes", type=int, default=4096)
     ap.add_argument("--preroll-s", type=float, default=0.3,
                     help="untimed steps for at least this long before the warmup (clock settling)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="no cpu_baseline (measured under --full)")
     ap.add_argument("--cpu-sample-leaves", type=int, default=1 << 20)
-    ap.add_argument("--verify", action="store_true", help="check the root against the C oracle")
+    ap.add_argument("--verify", action="store_true", help="check the roots against the committed oracle roots (as --full does) and, for "
+                                                             "a shape they do not cover, against the C oracle at run time")
     ap.add_argument("--dist", action="store_true",
                     help="join the RCCL group and all-gather the roots even at world size 1 (exercises the N > 1 path on one GPU)")
     ap.add_argument("--gather", choices=["batch", "step"], default="batch",
@@ -204,13 +219,13 @@ def parse(argv=None):
                     help="record the kernel-timing events on every k-th step of the timed loop only "
                          "(NKV_OPT_TIMING_EVERY; each record is a packet between two kernels)")
     ap.add_argument("--no-capi", action="store_true",
-                    help="no capi_group / capi_one_tree sub-records (by default rank 0 runs the one-process C-ABI "
+                    help="no capi_group / capi_one_tree sub-records (under --full rank 0 runs the one-process C-ABI "
                          "group over the same N GPUs in a fresh child process once the ranks are done)")
     ap.add_argument("--capi-timeout", type=int, default=150,
                     help="seconds per C-ABI group child (a healthy 8-GPU child takes well under a minute; a hung "
                          "one must not cost the run its line)")
     ap.add_argument("--no-subconfigs", action="store_true",
-                    help="no config2_mixed / config1_records sub-records (by default the N = 1 configs[1] line "
+                    help="no config2_mixed / config1_records sub-records (under --full the N = 1 configs[1] line "
                          "runs both in fresh children, each with its own roofline and CPU baseline)")
     ap.add_argument("--child-budget-s", type=int, default=360,
                     help="seconds after the ranks finish within which the sub-config children must start")
@@ -599,6 +614,69 @@ def build_tables(args, torch, _lib, L, ctx, rank, T, device="cuda"):
     return tabs
 
 
+DUMP_BYTES = 48 << 20  # --dump-outputs: float32 bytes of sampled node rows in all (the whole dump stays under 64 MB)
+DUMP_TOP_ROWS = 4096  # the last rows of a table's node array (its upper levels and the root) are always dumped
+DUMP_SEED = 0x6E616B68
+
+
+def dump_index(total, rows):
+    """The node rows --dump-outputs keeps of a table with `total` nodes: all of
+    them if they fit in `rows`, else the top DUMP_TOP_ROWS and a uniform draw
+    (seed DUMP_SEED) of the rest; ascending, the same in every run."""
+    import numpy as np
+    if total <= rows:
+        return np.arange(total, dtype=np.int64)
+    top = min(DUMP_TOP_ROWS, rows)
+    rng = np.random.default_rng(DUMP_SEED)
+    low = np.sort(rng.choice(total - top, size=rows - top, replace=False)).astype(np.int64)
+    return np.concatenate([low, np.arange(total - top, total, dtype=np.int64)])
+
+
+def roots_array(hex_roots):
+    """Hex roots -> (k, 20) float32, one byte per element."""
+    import numpy as np
+    return np.array([list(bytes.fromhex(r)) for r in hex_roots], dtype=np.float32).reshape(len(hex_roots), 20)
+
+
+def table_outputs(torch, tabs, root_only, budget):
+    """What a caller of the timed path holds after a step over `tabs` (the
+    tables of build_tables, on any device), as host arrays for --dump-outputs:
+    roots (T, 20); nodes_sample (T, S, 20), the node rows nodes_sample_index
+    (S) of every table's digest array, within `budget` float32 bytes;
+    record_err (T) and crc_stats (T, 3), the records configs' device words.
+    One byte per element.  root_only: the path leaves a root and no levels
+    (one_tree)."""
+    import numpy as np
+    outs = {"roots": np.stack([t["nodes"][-20:].cpu().numpy() for t in tabs]).astype(np.float32)}
+    if not root_only:
+        rows = max(1, budget // (80 * len(tabs)))
+        same = len({t["nodes"].numel() for t in tabs}) == 1  # ragged tables differ in size: one pair of files each
+        for i, t in enumerate(tabs):
+            idx = dump_index(t["nodes"].numel() // 20, rows)
+            got = t["nodes"].view(-1, 20)[torch.from_numpy(idx).to(t["nodes"].device)].cpu().numpy()
+            if same:
+                outs["nodes_sample_index"] = idx.astype(np.float64)
+                outs.setdefault("nodes_sample", []).append(got)
+            else:
+                outs[f"nodes_sample_index_t{i}"] = idx.astype(np.float64)
+                outs[f"nodes_sample_t{i}"] = got.astype(np.float32)
+        if same:
+            outs["nodes_sample"] = np.stack(outs["nodes_sample"]).astype(np.float32)
+    if "d_err" in tabs[0]:
+        outs["record_err"] = np.array([int(t["d_err"].item()) for t in tabs], dtype=np.float64)
+    if "d_stats" in tabs[0]:
+        outs["crc_stats"] = np.array([t["d_stats"].cpu().tolist() for t in tabs], dtype=np.float64)
+    return outs
+
+
+def dump_outputs(directory, outs, rank=0):
+    """--dump-outputs: DIR/<name>.npy for every array (rank r > 0: <name>_rank<r>.npy)."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    for name, a in outs.items():
+        np.save(os.path.join(directory, name + (f"_rank{rank}" if rank else "") + ".npy"), a)
+
+
 def valu_kind(config):
     """Which VALU_PER_WAVE_BLOCK entry a config's leaf kernel is priced at."""
     return {"records_verify": "verify", "records": "records"}.get(config, "leaf")
@@ -723,6 +801,9 @@ def main():
     if out is None:  # not rank 0: done
         return
     progress(f"{args.config}: ranks done, {out.get('value')} GiB/s")
+    if not args.full:  # the plain run: the headline line alone
+        print(json.dumps(out), flush=True)
+        return
     import gc
     import torch
     gc.collect()  # the tables and their closures hold this run's device buffers
@@ -783,6 +864,20 @@ SUB_KEYS = ("value", "unit", "n_gpus", "steps", "ms_per_step", "sclk_mhz", "roof
             "first_flush_no_reserve", "bound_note")
 
 
+def child_argv():
+    """This run's flags for a child process, less --dump-outputs (the dump is
+    the parent's own timed path's)."""
+    argv, skip = [], False
+    for a in sys.argv[1:]:
+        if skip:
+            skip = False
+        elif a == "--dump-outputs":
+            skip = True
+        elif not a.startswith("--dump-outputs="):
+            argv.append(a)
+    return argv
+
+
 def sub_child(args, config, timeout, run=None):
     """Run `bench.py --config <config> --gpus 1` (this run's step flags) in a
     fresh child and return the keys of its line that go into the parent's line
@@ -790,7 +885,7 @@ def sub_child(args, config, timeout, run=None):
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in CHILD_ENV_DROP}
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
-    cmd = [sys.executable, os.path.abspath(__file__)] + list(sys.argv[1:]) + [
+    cmd = [sys.executable, os.path.abspath(__file__)] + child_argv() + [
         "--config", config, "--gpus", "1", "--tables", "1", "--no-capi", "--no-subconfigs"]
     t0 = time.perf_counter()
     try:
@@ -818,7 +913,7 @@ CAPI_KEYS = ("value", "unit", "n_gpus", "steps", "ms_per_step", "backend", "sclk
 def capi_cmd(args, world, extra):
     """The C-ABI group child's command line: this run's flags with the group
     backend over `world` GPUs (later flags win in argparse)."""
-    argv = [a for a in sys.argv[1:]]
+    argv = child_argv()
     return [sys.executable, os.path.abspath(__file__)] + argv + ["--backend", "capi", "--gpus", str(world),
                                                                   "--no-cpu-baseline"] + list(extra)
 
@@ -967,7 +1062,12 @@ def run_ranks(args, T):
     sclk, clock_waves = ctx.clock() if not args.no_clock else (None, 0)
     calls, leaf_ms_tot, reduce_ms_tot = ctx.timing_summary()
     ctx.set_timing(False)
-    if calls == 0:  # kernel split measured in a separate loop of the same steps
+    if args.dump_outputs:  # what the last timed step left: every table's nodes (and the records configs' words)
+        outs = table_outputs(torch, tabs, one_tree, DUMP_BYTES // world)
+        if rg.dist:
+            outs["gathered_roots"] = rg.last_roots().cpu().numpy().reshape(world, 20).astype("float32")
+        dump_outputs(args.dump_outputs, outs, rank)
+    if calls == 0 and args.full:  # kernel split measured in a separate loop of the same steps
         ctx.set_timing(True)
         for _ in range(args.steps):
             step()
@@ -987,20 +1087,25 @@ def run_ranks(args, T):
     leaf_ms = leaf_ms_tot / max(calls, 1)
     reduce_ms = reduce_ms_tot / max(calls, 1)
 
-    # K3 (Serialize image) timed separately: not part of the metric
-    img = torch.empty(L.nkv_bfs_size(n), dtype=torch.uint8, device="cuda")
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    _lib.check(L.nkv_bfs_image_dev(ctx.h, nodes.data_ptr(), n, img.data_ptr()))
-    e0.record(stream)
-    for _ in range(5):
+    # K3 (Serialize image) timed separately, under --full: not part of the metric
+    bfs_ms = None
+    if args.full:
+        img = torch.empty(L.nkv_bfs_size(n), dtype=torch.uint8, device="cuda")
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         _lib.check(L.nkv_bfs_image_dev(ctx.h, nodes.data_ptr(), n, img.data_ptr()))
-    e1.record(stream)
-    torch.cuda.synchronize()
-    bfs_ms = e0.elapsed_time(e1) / 5
+        e0.record(stream)
+        for _ in range(5):
+            _lib.check(L.nkv_bfs_image_dev(ctx.h, nodes.data_ptr(), n, img.data_ptr()))
+        e1.record(stream)
+        torch.cuda.synchronize()
+        bfs_ms = e0.elapsed_time(e1) / 5
 
-    # every rank's roots against the committed oracle roots (no flag needed;
-    # VERDICT r03 item 1): one code per rank, gathered to all ranks
-    if one_tree:  # every rank reduced the top levels itself (sharded_tree): its root must be the tree's
+    # every rank's roots against the committed oracle roots (under --full or
+    # --verify): one code per rank, gathered to all ranks
+    check = args.full or args.verify
+    if not check:
+        code = -1
+    elif one_tree:  # every rank reduced the top levels itself (sharded_tree): its root must be the tree's
         want1 = expected_one_tree(n, vlen, world)
         code = -1 if want1 is None else int(root == want1)
     else:
@@ -1012,7 +1117,7 @@ def run_ranks(args, T):
         crc_stats = [t["d_stats"].cpu().tolist() for t in tabs]
         if any(st != [0, -1, 0] for st in crc_stats):
             code = 0
-    codes = rank_codes(dist if use_dist else None, world, rank, code, "cuda")
+    codes = rank_codes(dist if use_dist else None, world, rank, code, "cuda") if check else [-1] * world
     verified = verdict(codes)
     if args.verify and rank == 0 and verified is None:
         import numpy as np
@@ -1034,7 +1139,8 @@ def run_ranks(args, T):
         total_bytes = nbytes * world * args.steps
         value = total_bytes / elapsed / 2**30
         table_bytes = t0_["nbytes"]
-        achieved = table_bytes / (leaf_ms * 1e-3) / 1e9  # algorithmic payload bytes per K1 launch
+        # algorithmic payload bytes per K1 launch (None: --no-kernel-timing without --full, no K1 duration)
+        achieved = table_bytes / (leaf_ms * 1e-3) / 1e9 if calls else None
         ceiling = valu_ceiling(sclk, valu_kind(args.config))
         traffic, traffic_bounds = pmc_traffic(args, n, vlen, table_bytes)
         out = {
@@ -1067,10 +1173,10 @@ def run_ranks(args, T):
             "roofline": {
                 "bound": "hbm",
                 "kernel": kernel_text(args, T),
-                "achieved": round(achieved, 1),
+                "achieved": round(achieved, 1) if achieved else None,
                 "peak": HBM_PEAK_GBS,
                 "unit": "GB/s",
-                "frac": round(achieved / HBM_PEAK_GBS, 4),
+                "frac": round(achieved / HBM_PEAK_GBS, 4) if achieved else None,
                 # the whole step (leaf + tree + launches, N ranks): payload per
                 # GPU / ms_per_step / peak
                 "step_frac": round(nbytes / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBS, 4),
@@ -1082,10 +1188,11 @@ def run_ranks(args, T):
                 "valu_ceiling_basis": (f"{SIMDS} SIMDs x {sclk:.0f} MHz / ({VALU_PER_WAVE_BLOCK[valu_kind(args.config)]}"
                                        f" VALU per wave-block x {VALU_CYCLES:g} cycles) x 4096 B") if ceiling else
                                       "tools/sha1_rate.hip at 2.37 GHz (no clock reading)",
-                "valu_frac": round(achieved / (ceiling or SHA1_VALU_CEILING_GBS), 4),
+                "valu_frac": round(achieved / (ceiling or SHA1_VALU_CEILING_GBS), 4) if achieved else None,
             },
-            "kernel_ms": {"leaf": round(leaf_ms, 4), "tree_reduce": round(reduce_ms, 4),
-                          "bfs_image": round(bfs_ms, 4)},
+            "kernel_ms": {"leaf": round(leaf_ms, 4) if calls else None,
+                          "tree_reduce": round(reduce_ms, 4) if calls else None,
+                          "bfs_image": round(bfs_ms, 4) if bfs_ms is not None else None},
             "clock_probe_waves": clock_waves,
             "root": root,
             "cpu_baseline": None,
@@ -1097,7 +1204,7 @@ def run_ranks(args, T):
             out["roofline"].update({"chain_floor_ms": round(floor_ms, 4),
                                     "chain_floor_basis": f"longest value {longest} compressions x "
                                                          f"{LONE_WAVE_CYCLES_PER_BLOCK:g} cycles at {sclk:.0f} MHz",
-                                    "chain_frac": round(floor_ms / leaf_ms, 4)})
+                                    "chain_frac": round(floor_ms / leaf_ms, 4) if calls else None})
         if crc_stats is not None:
             out["crc_checked"] = {"records_per_table": n, "tables": T,
                                   "crc_mismatches": sum(st[0] for st in crc_stats),
@@ -1216,6 +1323,8 @@ def main_api_flush(args):
         },
     }
     out.update(vs_cpu(b["gib_s"], cpu))
+    if args.dump_outputs:  # the root of the last flush (the image goes to a file the driver removes)
+        dump_outputs(args.dump_outputs, {"roots": roots_array([runs["pool"][-1]["root"]])})
     print(json.dumps(out), flush=True)
 
 
@@ -1329,6 +1438,8 @@ def main_small_flush(args):
         "verified_vs_oracle": verified,
         "cpu_model": cpu_model(),
     }
+    if args.dump_outputs:  # every shape's root in the first mode timed
+        dump_outputs(args.dump_outputs, {"roots": roots_array([g["root"] for g in gpu[modes[0]]])})
     print(json.dumps(out), flush=True)
 
 
@@ -1408,6 +1519,13 @@ def main_capi(args, T):
     sclk, clock_waves = ctxs[0].clock() if not args.no_clock else (None, 0)
     calls, leaf_ms_tot, _ = ctxs[0].timing_summary()
     ctxs[0].set_timing(False)
+    if args.dump_outputs:
+        for m in range(N):
+            torch.cuda.synchronize(m)
+        if one_tree:  # every member's root of the one tree
+            dump_outputs(args.dump_outputs, {"roots": np.stack([d.cpu().numpy() for d in d_root]).astype(np.float32)})
+        else:
+            dump_outputs(args.dump_outputs, table_outputs(torch, order, False, DUMP_BYTES))
     # the gathered roots of the last step, checked against each table's own
     # nodes; every member's roots against the committed oracle roots
     members_agree = None

@@ -251,7 +251,7 @@ def test_merged_line_shape(monkeypatch, capsys):
     """main() on rank 0: the ranks' line + capi_group + capi_one_tree + the CPU
     baseline, one JSON line (stand-ins for the GPU run and the children)."""
     monkeypatch.delenv("WORLD_SIZE", raising=False)
-    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--full"])
     base = {"metric": "m", "value": 1.0, "n_gpus": 1, "verified_vs_oracle": True,
             "verified_ranks": [True], "cpu_baseline": None}
     monkeypatch.setattr(bench, "run_ranks", lambda args, T: dict(base))
@@ -294,7 +294,7 @@ def test_merged_line_at_n_gpus_keeps_cpu_baseline(monkeypatch, capsys):
     """Under the launcher (N = 8, rank 0) the CPU baseline is still measured,
     and runs4 gets the group sub-record but no one-tree run."""
     monkeypatch.setenv("WORLD_SIZE", "8")
-    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "8", "--config", "runs4", "--no-capi"])
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "8", "--config", "runs4", "--no-capi", "--full"])
     monkeypatch.setattr(bench, "run_ranks", lambda args, T: {"n_gpus": 8, "value": 8.0})
     monkeypatch.setattr(bench, "capi_child", lambda *a, **k: pytest.fail("--no-capi"))
     monkeypatch.setattr(bench, "cpu_baseline", lambda a: {"value": 1.0, "cores": 1, "port_1core": {"value": 1.0}})
@@ -489,3 +489,102 @@ def test_records_cpu_sample_layout():
                      "--value-bytes", "1024"])
     s = bench.cpu_sample(a)
     assert s["n"] == 1024 and int(s["lens"][0]) == 1024 - 30 - 16 and int(s["off"][1]) == 1024 + 46
+
+
+# ---------------------------------------------------------------------------
+# the plain run, --full and --dump-outputs
+
+def test_plain_run_prints_the_headline_line_only(monkeypatch, capsys):
+    """Without --full main() prints the ranks' line as it is: no group or
+    sub-config child, no CPU baseline."""
+    monkeypatch.delenv("WORLD_SIZE", raising=False)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    base = {"metric": "m", "value": 1.0, "unit": "GiB/s", "higher_is_better": True, "dtype": "u32",
+            "ms_per_step": 1.25, "n_gpus": 1, "cpu_baseline": None}
+    seen = []
+    monkeypatch.setattr(bench, "run_ranks", lambda args, T: seen.append(args.full) or dict(base))
+    monkeypatch.setattr(bench, "capi_child", lambda *a, **k: pytest.fail("--full only"))
+    monkeypatch.setattr(bench, "sub_child", lambda *a, **k: pytest.fail("--full only"))
+    monkeypatch.setattr(bench, "cpu_baseline", lambda a: pytest.fail("--full only"))
+    bench.main()
+    assert seen == [False]
+    assert json.loads(capsys.readouterr().out.strip().splitlines()[-1]) == base
+
+
+def test_children_inherit_full_but_not_the_dump(monkeypatch):
+    """A child gets this run's flags, --full among them, but never
+    --dump-outputs: the dump is the parent's own last step."""
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "7", "--dump-outputs", "d", "--full", "--dump-outputs=e"])
+    assert bench.child_argv() == ["--steps", "7", "--full"]
+    args = bench.parse(sys.argv[1:])
+    assert args.full and args.dump_outputs == "e" and args.steps == 7
+    child = bench.parse(bench.capi_cmd(args, 2, [])[2:])
+    assert child.full and child.dump_outputs is None and child.backend == "capi" and child.gpus == 2
+    plain = bench.parse(["--gpus", "1", "--steps", "5", "--warmup", "2"])
+    assert not plain.full and plain.dump_outputs is None
+
+
+def test_dump_index_is_fixed_and_keeps_the_top_rows():
+    """The sampled node rows: every row of a small table; of a large one the
+    top rows (upper levels, root) and the same seeded draw in every run."""
+    import numpy as np
+    assert np.array_equal(bench.dump_index(1999, 4096), np.arange(1999))
+    total, rows = (2 << 20) - 1, bench.DUMP_BYTES // 80
+    a, b = bench.dump_index(total, rows), bench.dump_index(total, rows)
+    assert np.array_equal(a, b) and len(a) == rows and np.all(np.diff(a) > 0)
+    assert np.array_equal(a[-bench.DUMP_TOP_ROWS:], np.arange(total - bench.DUMP_TOP_ROWS, total))
+    assert rows * 80 <= bench.DUMP_BYTES < 64 << 20
+
+
+def test_dump_outputs_files(tmp_path):
+    """table_outputs + dump_outputs over stand-in tables (CPU tensors): float32
+    / float64 .npy files holding the roots, the sampled rows and the records
+    words, one byte per element."""
+    import numpy as np
+    import torch
+    g = torch.Generator().manual_seed(5)
+    tabs = [{"nodes": torch.randint(0, 256, (1999 * 20,), dtype=torch.uint8, generator=g),
+             "d_err": torch.zeros(1, dtype=torch.int32),
+             "d_stats": torch.tensor([0, -1, 0], dtype=torch.int64)} for _ in range(2)]
+    budget = 2 * 500 * 80  # 500 rows per table
+    bench.dump_outputs(str(tmp_path / "o"), bench.table_outputs(torch, tabs, False, budget))
+    got = {f[:-4]: np.load(tmp_path / "o" / f) for f in os.listdir(tmp_path / "o")}
+    assert sorted(got) == ["crc_stats", "nodes_sample", "nodes_sample_index", "record_err", "roots"]
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    idx = got["nodes_sample_index"].astype(np.int64)
+    assert np.array_equal(idx, bench.dump_index(1999, 500)) and got["nodes_sample"].shape == (2, 500, 20)
+    for t in range(2):
+        rows = tabs[t]["nodes"].view(-1, 20).numpy()
+        assert np.array_equal(got["nodes_sample"][t], rows[idx]) and np.array_equal(got["roots"][t], rows[-1])
+    assert got["crc_stats"].tolist() == [[0, -1, 0]] * 2 and got["record_err"].tolist() == [0, 0]
+    # a path that leaves a root only; another rank's files carry its number
+    bench.dump_outputs(str(tmp_path / "o"), bench.table_outputs(torch, tabs[:1], True, budget), rank=3)
+    assert sorted(set(os.listdir(tmp_path / "o")) - {k + ".npy" for k in got}) == [
+        "crc_stats_rank3.npy", "record_err_rank3.npy", "roots_rank3.npy"]
+    assert np.array_equal(bench.roots_array(["00ff10" + "00" * 17])[0, :3], [0, 255, 16])
+
+
+@pytest.mark.gpu
+def test_plain_run_dumps_its_last_step(oracle, tmp_path):
+    """A plain run on the GPU at a small ragged shape: --steps sets the timed
+    steps, the line has the headline keys and none of --full's, and the dumped
+    node rows are the oracle's tree over the same seeded values."""
+    import subprocess
+    import numpy as np
+    n, vlen = 3001, 1024
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                          "--preroll-s", "0", "--leaves", str(n), "--value-bytes", str(vlen),
+                          "--dump-outputs", str(tmp_path / "o")], capture_output=True, text=True, timeout=240)
+    assert out.returncode == 0, out.stderr[-2000:]
+    line = json.loads(out.stdout.strip().splitlines()[-1])
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["unit"] == "GiB/s" and line["dtype"] == "u32"
+    assert abs(line["value"] - n * vlen / (line["ms_per_step"] * 1e-3) / 2**30) <= 0.02 * line["value"] + 0.01
+    assert line["cpu_baseline"] is None and line["verified_vs_oracle"] is None
+    assert not any(k in line for k in ("capi_group", "config2_mixed", "api_flush"))
+    data = oracle.splitmix64_bytes(n * vlen, bench.SEED)
+    want = oracle.tree_from_digests(oracle.leaf_hashes_strided(data, vlen, vlen, n))
+    idx = np.load(tmp_path / "o" / "nodes_sample_index.npy").astype(np.int64)
+    got = np.load(tmp_path / "o" / "nodes_sample.npy")
+    assert got.dtype == np.float32 and np.array_equal(idx, np.arange(len(want)))
+    assert np.array_equal(got[0], want) and np.array_equal(np.load(tmp_path / "o" / "roots.npy")[0], want[-1])
+    assert line["root"] == want[-1].tobytes().hex()

@@ -360,7 +360,7 @@ def test_bench_nccl_world_n(world):
     sys.path.insert(0, ROOT)
     import bench
     cmd = bench.launcher_cmd(["--gpus", str(world), "--steps", "3", "--warmup", "1", "--preroll-s", "0",
-                              "--no-cpu-baseline"], world, _free_port())
+                              "--full", "--no-cpu-baseline"], world, _free_port())
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     out = subprocess.run(cmd, stdout=subprocess.PIPE, text=True, timeout=850, env=env)
     assert out.returncode == 0
