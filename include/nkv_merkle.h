@@ -406,6 +406,60 @@ int nkv_bloom_query_dev(nkv_ctx *ctx, const void *d_keys, const uint64_t *d_off,
 /* synthetic input: byte j = byte (j % 8) of splitmix64(seed, j / 8) */
 int nkv_fill_splitmix64_dev(nkv_ctx *ctx, void *d_buf, uint64_t nbytes, uint64_t seed);
 
+/* ---- compaction merge (core/lsmtree/lsmtree.go:137-231) ----
+ * k sorted runs of one level in, one Data table out.  A run is a Data-table
+ * stream of whole serialized records (record.go:191-199) whose keys increase
+ * strictly under bytes.Compare (unsigned lexicographic; a proper prefix sorts
+ * first, the empty key is smallest).  The output holds one record per distinct
+ * key in ascending key order, each copied byte for byte from its input (header,
+ * stored Crc, Status and TypeInfo untouched).  Tombstones are kept: merge never
+ * looks at Status.
+ *
+ * Among the records of one key the greatest Timestamp wins, compared as signed
+ * int64.  Timestamps are whole seconds, so ties across runs are ordinary; the
+ * reference settles them by the order in which the records entered its queue
+ * (its sort of at most 6 elements is a stable insertion sort), which has this
+ * closed form: the winner is the minimum under (Timestamp descending, then the
+ * key of the record's predecessor in its own run ascending with "no
+ * predecessor" smallest, then run index ascending).  For k > 6 the reference's
+ * own result on a tie depends on the internals of its Go release's sort and is
+ * not pinned; the library applies the closed form for every k.
+ *
+ * Errors: NKV_ERR_INVALID for k outside 1..NKV_MERGE_MAX_RUNS, a null pointer,
+ * more than 2^31 - 1 records in all, out_cap below the sum of stream_len, and
+ * for a run whose keys are not strictly increasing, whose header sizes reach
+ * outside its stream, or whose records do not each end where the next one
+ * starts (the first at 0, the last at stream_len).  The runs are validated by
+ * a kernel of their own before any kernel follows a key or copies a record;
+ * when it refuses, nothing further is launched and the context stays usable.
+ * Empty runs (n = 0, stream_len = 0) are allowed; when every run is empty the
+ * call returns NKV_OK with *n_out = 0 (the zero-leaf error belongs to the tree
+ * call that would follow). */
+#define NKV_MERGE_MAX_RUNS 16
+typedef struct nkv_run { /* all pointers on the context's device */
+    const void *stream;
+    uint64_t stream_len;
+    const uint64_t *rec_off; /* n record offsets, as nkv_record_offsets_dev writes them */
+    uint64_t n;
+} nkv_run;
+/* Device-resident form.  d_out (out_cap >= sum of stream_len bytes, any
+ * alignment) receives the merged stream, d_out_off (sum of n entries) the
+ * offset of each output record, d_out_src (nullable, sum of n entries)
+ * (run << 32) | index of the input record each output record was copied from.
+ * *n_out / *out_len (host): records and bytes written; the call synchronizes.
+ * d_out / d_out_off feed nkv_tree_from_records_dev, nkv_record_crc_dev and
+ * nkv_bloom_insert_records_dev as they are.  Under NKV_TIMING_EVENTS the "leaf"
+ * interval is rank + scans + scatter and the "reduce" interval the copy kernel. */
+int nkv_merge_records_dev(nkv_ctx *ctx, const nkv_run *runs, int k, void *d_out, uint64_t out_cap,
+                          uint64_t *d_out_off, uint64_t *d_out_src, uint64_t *n_out, uint64_t *out_len);
+/* Host-memory form: run r is streams[r] (stream_len[r] bytes) with the RecSize
+ * of each of its n[r] records in rec_size[r] (they must add up to stream_len[r]);
+ * out (out_cap >= sum of stream_len) and out_rec_size (sum of n entries)
+ * receive the merged table. */
+int nkv_merge_records(nkv_ctx *ctx, const uint8_t *const *streams, const uint64_t *stream_len,
+                      const uint64_t *const *rec_size, const uint64_t *n, int k, uint8_t *out,
+                      uint64_t out_cap, uint64_t *out_rec_size, uint64_t *n_out, uint64_t *out_len);
+
 /* ---- several tables per call (compaction's runs, consecutive flushes) ----
  * One table of device-resident leaves, described for nkv_trees_dev /
  * nkv_group_trees_dev (all pointers on the device that builds it). */

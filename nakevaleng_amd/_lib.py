@@ -74,6 +74,12 @@ class NkvValues(ctypes.Structure):
                 ("img_out", _vp)]
 
 
+class NkvRun(ctypes.Structure):
+    """struct nkv_run: one device-resident sorted run (nkv_merge_records_dev)."""
+    _fields_ = [("stream", _vp), ("stream_len", _u64), ("rec_off", _vp), ("n", _u64)]
+
+
+NKV_MERGE_MAX_RUNS = 16
 _tabp = ctypes.POINTER(NkvTable)
 
 # name -> (restype, argtypes); every symbol include/nkv_merkle.h declares
@@ -136,6 +142,9 @@ SIGNATURES = {
     "nkv_bloom_query_dev": (_int, [_vp, _vp, _vp, _vp, _u64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
                                    _vp, _vp]),
     "nkv_fill_splitmix64_dev": (_int, [_vp, _vp, _u64, _u64]),
+    "nkv_merge_records_dev": (_int, [_vp, ctypes.POINTER(NkvRun), _int, _vp, _u64, _vp, _vp, _u64p, _u64p]),
+    "nkv_merge_records": (_int, [_vp, ctypes.POINTER(_vp), _u64p, ctypes.POINTER(_vp), _u64p, _int, _vp, _u64, _vp,
+                                 _u64p, _u64p]),
     "nkv_ctx_clock": (_int, [_vp, ctypes.POINTER(ctypes.c_double), _u64p]),
     "nkv_ctx_last_host_timing": (_int, [_vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float),
                                         ctypes.POINTER(ctypes.c_float)]),

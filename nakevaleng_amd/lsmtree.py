@@ -6,7 +6,11 @@ output table's tree in MakeTableSecondaries (sstable.go:41-46).  Independent
 table builds are independent trees, so they shard with no data-path exchange:
 one process per GPU builds its tables, then the 20-byte roots are all-gathered
 (RCCL over xGMI when the process group is "nccl"; gloo in CPU tests) so every
-rank holds every table's root.  The k-way merge itself stays on the host.
+rank holds every table's root.
+
+The k-way merge itself (lsmtree.go:137-231) runs on the device too: merge() is
+its host-memory form, compact() uploads the runs once and chains the checksum
+check, the merge, the output table's tree and its filter with no re-upload.
 """
 from __future__ import annotations
 
@@ -112,3 +116,134 @@ def compact_roots(tables: Sequence[Table], build: Callable[[Table, int], bytes] 
         return [local[i] for i in range(len(tables))]
     import torch
     return gather_roots(local, len(tables), torch.device("cuda", dev))
+
+
+# ---------------------------------------------------------------------------
+# the merge itself (nkv_merge_records / nkv_merge_records_dev)
+
+def _check_runs(tables) -> None:
+    from . import _lib
+    if not 1 <= len(tables) <= _lib.NKV_MERGE_MAX_RUNS:
+        raise ValueError(f"merge takes 1..{_lib.NKV_MERGE_MAX_RUNS} runs, got {len(tables)}")
+
+
+def merge(tables: Sequence[Table], device=None) -> Table:
+    """lsmtree.merge (lsmtree.go:137-231) of k sorted runs held in host memory:
+    one record per distinct key in ascending key order, the newest Timestamp
+    winning (ties as include/nkv_merkle.h states), tombstones kept, every
+    record copied byte for byte.  Returns the merged (stream, RecSize array)."""
+    import ctypes
+    from . import _lib
+    _check_runs(tables)
+    k = len(tables)
+    ctx = _lib.default_context(rank_device(device))
+    bufs = [np.frombuffer(bytes(t[0]) + b"\0", dtype=np.uint8) for t in tables]
+    sizes = [np.ascontiguousarray(t[1], dtype=np.uint64) for t in tables]
+    sizes_p = [s if s.size else np.zeros(1, np.uint64) for s in sizes]
+    lens = np.asarray([b.size - 1 for b in bufs], dtype=np.uint64)
+    ns = np.asarray([s.size for s in sizes], dtype=np.uint64)
+    streams = (ctypes.c_void_p * k)(*[b.ctypes.data for b in bufs])
+    rec_size = (ctypes.c_void_p * k)(*[s.ctypes.data for s in sizes_p])
+    out = np.zeros(int(lens.sum()) + 1, np.uint8)
+    out_sizes = np.zeros(int(ns.sum()) + 1, np.uint64)
+    n_out, out_len = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    _lib.check(_lib.lib().nkv_merge_records(ctx.h, streams, _lib.p64(lens), rec_size, _lib.p64(ns), k,
+                                            out.ctypes.data, out.size - 1, out_sizes.ctypes.data,
+                                            ctypes.byref(n_out), ctypes.byref(out_len)), "compaction merge")
+    return out[:out_len.value].tobytes(), out_sizes[:n_out.value].copy()
+
+
+def compact(tables: Sequence[Table], device=None, seed: Optional[int] = None,
+            false_positive_rate: float = 0.01) -> dict:
+    """One compaction on the device, the runs uploaded once: every input
+    record's Crc checked (nkv_tree_verify_records_dev; a bad one raises
+    record.verify's "Bad Record checksum" ValueError before any merge is
+    launched), the k-way merge (nkv_merge_records_dev), the merged table's
+    Merkle tree and Serialize image (nkv_tree_from_records_dev,
+    nkv_bfs_image_dev) and, when `seed` is given, its filter
+    (nkv_bloom_insert_records_dev; bloomfilter.New(n, false_positive_rate)).
+
+    Returns {"table": (stream, RecSize array), "root": 20 bytes, "image":
+    bytes, "filter": BloomFilter or None, "sources": (run << 32) | index of
+    every output record}.  A merge of no records raises MerkleTreeError, as New
+    does on zero leaves."""
+    import ctypes
+    import torch
+    from . import _lib, bloomfilter
+    from .merkletree import MerkleTreeError
+    _check_runs(tables)
+    k = len(tables)
+    dev_index = rank_device(device)
+    ctx = _lib.default_context(dev_index)
+    L = _lib.lib()
+    dev = torch.device("cuda", dev_index)
+
+    def up(a):
+        return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).copy()).to(dev)
+
+    def u8(nbytes):
+        return torch.zeros(max(int(nbytes), 16), dtype=torch.uint8, device=dev)
+
+    stream = torch.cuda.current_stream(dev)
+    with ctx.on_stream(stream.cuda_stream):
+        runs = (_lib.NkvRun * k)()
+        keep = []
+        total = n_all = 0
+        for r, (data, rec_sizes) in enumerate(tables):
+            sizes = np.ascontiguousarray(rec_sizes, dtype=np.uint64)
+            n, nbytes = int(sizes.size), len(data)
+            if n == 0:
+                runs[r] = _lib.NkvRun(None, nbytes, None, 0)
+                continue
+            d_data = up(np.frombuffer(bytes(data), np.uint8))
+            d_size, d_off = up(sizes), u8(8 * n)
+            _lib.check(L.nkv_record_offsets_dev(ctx.h, d_size.data_ptr(), n, d_off.data_ptr()))
+            d_nodes, d_crc, d_stats = u8(L.nkv_total_nodes(n) * 20), u8(4 * n), u8(24)
+            _lib.check(L.nkv_tree_verify_records_dev(ctx.h, d_data.data_ptr(), nbytes, d_off.data_ptr(), n,
+                                                     d_nodes.data_ptr(), d_crc.data_ptr(), d_stats.data_ptr()),
+                       "compaction read")
+            bad, first, hdr = d_stats.cpu().numpy().view(np.uint64).tolist()
+            if hdr:
+                raise _lib.NkvError(_lib.NKV_ERR_INVALID, f"compaction read of run {r}")
+            if bad:
+                got = int(d_crc.cpu().numpy().view(np.uint32)[first])
+                stored = int(np.frombuffer(bytes(data), "<u4", 1, int(sizes[:first].sum()))[0])
+                raise ValueError(f"Bad Record checksum (got {got}, expected {stored})")
+            runs[r] = _lib.NkvRun(d_data.data_ptr(), nbytes, d_off.data_ptr(), n)
+            keep += [d_data, d_off]
+            total += nbytes
+            n_all += n
+        d_out, d_out_off, d_out_src = u8(total), u8(8 * n_all), u8(8 * n_all)
+        n_out, out_len = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        _lib.check(L.nkv_merge_records_dev(ctx.h, runs, k, d_out.data_ptr(), total, d_out_off.data_ptr(),
+                                           d_out_src.data_ptr(), ctypes.byref(n_out), ctypes.byref(out_len)),
+                   "compaction merge")
+        n, nbytes = n_out.value, out_len.value
+        if n == 0:
+            raise MerkleTreeError("cannot build Merkle Tree from 0 nodes")
+        d_nodes, d_img = u8(L.nkv_total_nodes(n) * 20), u8(L.nkv_bfs_size(n))
+        d_err = u8(4)
+        _lib.check(L.nkv_tree_from_records_dev(ctx.h, d_out.data_ptr(), nbytes, d_out_off.data_ptr(), n,
+                                               d_nodes.data_ptr(), d_err.data_ptr()), "compaction Merkle step")
+        _lib.check(L.nkv_bfs_image_dev(ctx.h, d_nodes.data_ptr(), n, d_img.data_ptr()), "Serialize image")
+        bf = d_bits = None
+        if seed is not None:
+            bf = bloomfilter.New(n, false_positive_rate, seed=seed, ctx=ctx)
+            d_bits = u8(((bf.M + 31) // 32) * 4)
+            _lib.check(L.nkv_bloom_insert_records_dev(ctx.h, d_out.data_ptr(), nbytes, d_out_off.data_ptr(), n,
+                                                      bf.M, bf.K, bf.HashSeeds[0] if bf.K else 0,
+                                                      d_bits.data_ptr()), "compaction filter")
+        stream.synchronize()
+    if int(d_err.cpu().numpy().view(np.uint32)[0]):
+        raise _lib.NkvError(_lib.NKV_ERR_INVALID, "compaction Merkle step")
+    off = d_out_off.cpu().numpy().view(np.uint64)[:n]
+    sizes = np.diff(np.append(off, np.uint64(nbytes))).astype(np.uint64)
+    nodes = d_nodes.cpu().numpy()
+    root_at = (L.nkv_total_nodes(n) - 1) * 20
+    if bf is not None:
+        bf._contents = bytearray(d_bits.cpu().numpy()[:(bf.M + 7) // 8].tobytes())
+    return {"table": (d_out.cpu().numpy()[:nbytes].tobytes(), sizes),
+            "root": nodes[root_at:root_at + 20].tobytes(),
+            "image": d_img.cpu().numpy()[:L.nkv_bfs_size(n)].tobytes(),
+            "filter": bf,
+            "sources": d_out_src.cpu().numpy().view(np.uint64)[:n].copy()}
