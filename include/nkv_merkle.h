@@ -50,6 +50,23 @@
  *     gathers chunk k+1 while chunk k is copied to the device.
  *   - *_dev functions take device pointers and are asynchronous on the
  *     context's stream (nkv_ctx_set_stream); nkv_ctx_sync() waits.
+ *   - Device outputs: an output buffer needs only the natural alignment of
+ *     what it holds, and a call writes exactly the documented extent of each
+ *     output, not a byte before or past it (callers pack nodes, images and
+ *     offset arrays next to each other in one allocation).
+ *       byte strings, at any address: d_img, nkv_bloom_query_dev's d_out, the
+ *         buffer of nkv_fill_splitmix64_dev, the merge's d_out;
+ *       digest arrays (d_nodes, nkv_table.nodes, d_roots and d_out entries of
+ *         the group calls), 4-byte aligned: level starts inside a nodes buffer
+ *         are multiples of 20 bytes, no more;
+ *       uint32_t arrays and filter words (d_crc, d_err, d_bits), 4-byte aligned;
+ *       uint64_t arrays (d_rec_off, d_voff, d_vlen, d_stats, d_out_off,
+ *         d_out_src), 8-byte aligned.
+ *     nkv_leaf_hash*_dev write level 0 only (20 n bytes); nkv_tree_reduce_dev
+ *     leaves level 0 as given; d_bits is ((m + 31) / 32) * 4 bytes; the merge
+ *     writes out_len bytes and n_out entries.  Inputs are never written:
+ *     values, record streams, offset and length arrays and the merge's runs
+ *     are read in place (at any alignment where they are bytes).
  *   - Thread safety: distinct contexts may be used concurrently; one context
  *     must not be used by two threads at once.  Every call re-binds the
  *     context's device (cgo calls may land on any OS thread).

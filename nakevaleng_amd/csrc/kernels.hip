@@ -1773,11 +1773,33 @@ __global__ __launch_bounds__(kBlock) void k_bfs_image(const uint8_t* __restrict_
         }
     }
     __syncthreads();
-    const uint64_t p0 = s0 + 16 * threadIdx.x;
-    if (p0 + 16 <= s1) {
-        *reinterpret_cast<uint4*>(img + p0) = *reinterpret_cast<const uint4*>(seg + 16 * threadIdx.x);
+    // The image is a byte string and may lie at any address (nkv_merkle.h,
+    // device outputs).  s0 is a multiple of 16, so every segment has the same
+    // sh bytes up to the first 16-byte boundary of img: those go out as bytes
+    // (as k_merge_copy's head does), then each thread stores the 16 aligned
+    // bytes at sh + 16 t, or the clipped rest of the segment as bytes.
+    // (Established by reading: the hardware also accepts misaligned 16-byte
+    // stores, so the placement tests pin the bytes and the extent, not this
+    // alignment handling.  Do not take it for guarded when simplifying.)
+    const uint32_t sh = uint32_t(-reinterpret_cast<uintptr_t>(img)) & 15u;
+    const uint32_t len = uint32_t(s1 - s0);
+    if (threadIdx.x < min(sh, len)) img[s0 + threadIdx.x] = seg[threadIdx.x];
+    const uint32_t c = sh + 16 * threadIdx.x;
+    if (c + 16 <= len) {
+        uint4 v;
+        if (sh == 0) {
+            v = *reinterpret_cast<const uint4*>(seg + c);
+        } else {
+            uint32_t w[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                w[k] = uint32_t(seg[c + 4 * k]) | uint32_t(seg[c + 4 * k + 1]) << 8 |
+                       uint32_t(seg[c + 4 * k + 2]) << 16 | uint32_t(seg[c + 4 * k + 3]) << 24;
+            v = make_uint4(w[0], w[1], w[2], w[3]);
+        }
+        *reinterpret_cast<uint4*>(img + s0 + c) = v;
     } else {
-        for (uint64_t p = p0; p < s1; ++p) img[p] = seg[p - s0];
+        for (uint32_t p = c; p < len; ++p) img[s0 + p] = seg[p];
     }
 }
 
@@ -2022,13 +2044,19 @@ __device__ __forceinline__ uint64_t splitmix64_at(uint64_t seed, uint64_t k) {
 __global__ __launch_bounds__(kBlock) void k_fill(uint8_t* __restrict__ buf, uint64_t nbytes,
                                                   uint64_t seed) {
     const uint64_t stride = uint64_t(gridDim.x) * kBlock;
+    // a byte string, at any address (nkv_merkle.h, device outputs): 16-byte
+    // stores only into a 16-byte aligned buffer.  (Established by reading: the
+    // hardware also accepts misaligned 16-byte stores, so the placement tests
+    // pin the bytes and the extent, not this check.)
+    const bool al = (reinterpret_cast<uintptr_t>(buf) & 15u) == 0;
     for (uint64_t t = uint64_t(blockIdx.x) * kBlock + threadIdx.x; 16 * t < nbytes; t += stride) {
         const uint64_t a = splitmix64_at(seed, 2 * t), b = splitmix64_at(seed, 2 * t + 1);
-        if (16 * t + 16 <= nbytes) {
+        if (al && 16 * t + 16 <= nbytes) {
             *reinterpret_cast<uint4*>(buf + 16 * t) =
                 make_uint4(uint32_t(a), uint32_t(a >> 32), uint32_t(b), uint32_t(b >> 32));
         } else {
-            for (uint64_t j = 16 * t; j < nbytes; ++j) {
+            const uint64_t j1 = min(16 * t + 16, nbytes);
+            for (uint64_t j = 16 * t; j < j1; ++j) {
                 const uint64_t v = (j - 16 * t) < 8 ? a : b;
                 buf[j] = uint8_t(v >> (8 * (j & 7)));
             }

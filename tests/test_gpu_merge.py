@@ -9,7 +9,7 @@ import pytest
 
 from nakevaleng_amd import record
 from tests.merge_ref import merge_closed
-from tests.test_merge_ref import HAND_CASES, rec
+from tests.test_merge_ref import BOUNDARY_SEEDS, HAND_CASES, boundary_case, boundary_coverage, rec
 
 pytestmark = pytest.mark.gpu
 
@@ -133,6 +133,34 @@ def test_fuzz(nkv, seed):
     rng = np.random.default_rng(0x6D72 + seed)
     k = [1, 2, 3, 4, 6, 16][seed % 6]
     check_merge(nkv, fuzz_runs(rng, k), shift_in=seed % 3, shift_out=(5 * seed) % 16, want_src=seed % 4 != 3)
+
+
+@pytest.mark.parametrize("seed", range(BOUNDARY_SEEDS))
+def test_fuzz_keys_at_prefix_boundary(nkv, seed):
+    """Keys over {0x00, 'a', 0xFF} that differ at or just past byte 8 (every
+    prefix of an 8-byte stem, the stem plus tails of 0..3 bytes, a second stem
+    that differs in byte 8): cmp_key's dense zero-padded prefix, its shortcut on
+    the lengths when a key has at most 8 bytes, and the byte loop behind it.
+    The CPU side (tests/test_merge_ref.py) asserts that merge_literal and
+    merge_closed agree for k <= 6 and that the 12 seeds hold at least 100 key
+    pairs with equal padded prefixes of either sort; here every seed's case
+    holds some."""
+    k, runs = boundary_case(seed)
+    short, long_, _, _ = boundary_coverage(runs)
+    assert short >= 1 and long_ >= 1
+    check_merge(nkv, runs, shift_in=seed % 3, shift_out=(5 * seed) % 16, want_src=seed % 4 != 3)
+
+
+def test_compact_of_empty_runs_raises_the_reference_error(nkv):
+    """Every run empty: the merge itself returns no records, and the tree step
+    that follows refuses with New's text (merkletree.go:20)."""
+    from nakevaleng_amd import lsmtree
+    from nakevaleng_amd.merkletree import MerkleTreeError
+    for k in (1, 3):
+        with pytest.raises(MerkleTreeError) as e:
+            lsmtree.compact([(b"", np.zeros(0, np.uint64))] * k, device=0)
+        assert str(e.value) == "cannot build Merkle Tree from 0 nodes"
+    _good(nkv)
 
 
 def test_sstable_shape_many_tiles(nkv):
@@ -308,6 +336,10 @@ BAD_RUNS = {
     "descending": lambda: _tab([rec(b"a"), rec(b"c"), rec(b"b")]),
     # long keys that differ after the dense 8-byte prefix only
     "descending_long": lambda: _tab([rec(b"0123456789b"), rec(b"0123456789a")]),
+    # the same 8 bytes: the longer key first
+    "descending_at_8": lambda: _tab([rec(b"abcdefgh\x00"), rec(b"abcdefgh")]),
+    # equal zero-padded prefixes, decided by the lengths: the longer key first
+    "equal_padded": lambda: _tab([rec(b"ab\x00"), rec(b"ab")]),
     "value_size_2_63": lambda: _patch(_tab([rec(b"a"), rec(b"b")]), 22, (1 << 63).to_bytes(8, "little")),
     "value_size_wraps": lambda: _patch(_tab([rec(b"a"), rec(b"b")]), 22, (2**64 - 20).to_bytes(8, "little")),
     "key_past_stream": lambda: _patch(_tab([rec(b"a"), rec(b"b")]), 32 + 14, (1000).to_bytes(8, "little")),
