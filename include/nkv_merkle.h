@@ -32,6 +32,8 @@
  *   record checksum         core/record/record.go:51 (New),     nkv_record_crc /
  *     crc32.ChecksumIEEE    :163-169 (Deserialize check)        nkv_record_crc_dev /
  *     over Key ++ Value                                         nkv_crc32_dev
+ *   makeIndexAndSummary     core/sstable/sstable.go:76-139      nkv_index_summary_dev /
+ *                                                               nkv_index_summary_from_records
  *
  * Conventions
  *   - Every function returns an nkv_status (0 = NKV_OK) unless noted; nothing
@@ -55,7 +57,8 @@
  *     output, not a byte before or past it (callers pack nodes, images and
  *     offset arrays next to each other in one allocation).
  *       byte strings, at any address: d_img, nkv_bloom_query_dev's d_out, the
- *         buffer of nkv_fill_splitmix64_dev, the merge's d_out;
+ *         buffer of nkv_fill_splitmix64_dev, the merge's d_out, d_index and
+ *         d_summary of nkv_index_summary_dev;
  *       digest arrays (d_nodes, nkv_table.nodes, d_roots and d_out entries of
  *         the group calls), 4-byte aligned: level starts inside a nodes buffer
  *         are multiples of 20 bytes, no more;
@@ -64,7 +67,8 @@
  *         d_out_src), 8-byte aligned.
  *     nkv_leaf_hash*_dev write level 0 only (20 n bytes); nkv_tree_reduce_dev
  *     leaves level 0 as given; d_bits is ((m + 31) / 32) * 4 bytes; the merge
- *     writes out_len bytes and n_out entries.  Inputs are never written:
+ *     writes out_len bytes and n_out entries; nkv_index_summary_dev writes
+ *     *index_len and *summary_len bytes.  Inputs are never written:
  *     values, record streams, offset and length arrays and the merge's runs
  *     are read in place (at any alignment where they are bytes).
  *   - Thread safety: distinct contexts may be used concurrently; one context
@@ -476,6 +480,56 @@ int nkv_merge_records_dev(nkv_ctx *ctx, const nkv_run *runs, int k, void *d_out,
 int nkv_merge_records(nkv_ctx *ctx, const uint8_t *const *streams, const uint64_t *stream_len,
                       const uint64_t *const *rec_size, const uint64_t *n, int k, uint8_t *out,
                       uint64_t out_cap, uint64_t *out_rec_size, uint64_t *n_out, uint64_t *out_len);
+
+/* ---- Index and Summary tables (core/sstable/sstable.go:76-139) ----
+ * makeIndexAndSummary over a Data table: for records i = 0..n-1 with key K_i
+ * of ks_i bytes,
+ *   Index    entry i = ks_i (u64 LE) | Offset (i64 LE) = the record's offset
+ *            in the Data table (d_rec_off[i] as given) | K_i, the entries
+ *            concatenated: index_len = 16 n + sum of ks_i bytes;
+ *   Summary  MinKeySize u64 | MaxKeySize u64 | Payload u64 | MinKey = K_0 |
+ *            MaxKey = K_(n-1), then one entry ks_i | Offset = the byte offset
+ *            of Index entry i in the Index | K_i for every selected i in
+ *            ascending order; record i is selected when i == 0, i % page_size
+ *            == 0 or i == n - 1 (once each); Payload = the bytes of all the
+ *            entries.  nkv_summary_entries(n, page_size) is their count: n for
+ *            n <= 1, else 1 + (n - 1) / page + ((n - 1) % page ? 1 : 0).
+ * n == 0 gives an empty Index and the 24 zero bytes of an empty header.
+ * page_size == 0 is NKV_ERR_INVALID for n >= 2 (the reference divides by it
+ * at i = 1) and accepted for n <= 1; nkv_summary_entries returns 0 for the
+ * refused case.  Keys are encoded as they come: no order check, duplicates
+ * and the empty key included.
+ *
+ * Device form.  d_stream / d_rec_off as for nkv_tree_from_records_dev (the
+ * merge's d_out / d_out_off as they are).  d_index / d_summary (any byte
+ * alignment) receive the images, *index_len / *summary_len (host) their
+ * lengths, and exactly those extents are written.  With d_index and d_summary
+ * both NULL the call is a size query: NKV_OK and the two lengths.  A kernel
+ * checks every header and key span against the stream first, and the host
+ * reads its verdict and the lengths once (the call's one synchronize) before
+ * any writer is launched: NKV_ERR_INVALID, and nothing written, for a header
+ * or a key that reaches outside the stream (lengths 0), and for index_cap <
+ * *index_len or summary_cap < *summary_len (the lengths still reported, so
+ * the caller can retry).  After NKV_OK the images are complete in stream
+ * order.  Also NKV_ERR_INVALID: n > 2^31 - 1, a NULL index_len / summary_len,
+ * one output NULL while its image is not empty, n (16 + stream_len) >= 2^64.
+ * For a well-formed table (every key inside its own record, the records not
+ * overlapping) index_cap = stream_len - 14 n is always enough: each record
+ * spends 30 header bytes where its Index entry spends 16.  Under
+ * NKV_TIMING_EVENTS the "leaf" interval is the measure kernel and the scans,
+ * the "reduce" interval the writers. */
+uint64_t nkv_summary_entries(uint64_t n, uint64_t page_size);
+int nkv_index_summary_dev(nkv_ctx *ctx, const void *d_stream, uint64_t stream_len,
+                          const uint64_t *d_rec_off, uint64_t n, uint64_t page_size, void *d_index,
+                          uint64_t index_cap, void *d_summary, uint64_t summary_cap,
+                          uint64_t *index_len, uint64_t *summary_len);
+/* Host-memory form: stream and rec_size as for nkv_tree_from_records (the sizes
+ * must add up to stream_len); uploads, runs the device form, copies the images
+ * back.  Size query and capacities as above. */
+int nkv_index_summary_from_records(nkv_ctx *ctx, const uint8_t *stream, uint64_t stream_len,
+                                   const uint64_t *rec_size, uint64_t n, uint64_t page_size,
+                                   uint8_t *index_out, uint64_t index_cap, uint8_t *summary_out,
+                                   uint64_t summary_cap, uint64_t *index_len, uint64_t *summary_len);
 
 /* ---- several tables per call (compaction's runs, consecutive flushes) ----
  * One table of device-resident leaves, described for nkv_trees_dev /

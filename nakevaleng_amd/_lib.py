@@ -80,6 +80,7 @@ class NkvRun(ctypes.Structure):
 
 
 NKV_MERGE_MAX_RUNS = 16
+INDEX_WRITE_TILE = 16384  # csrc/index.hip kWriteTile: image bytes one writer workgroup owns
 _tabp = ctypes.POINTER(NkvTable)
 
 # name -> (restype, argtypes); every symbol include/nkv_merkle.h declares
@@ -145,6 +146,10 @@ SIGNATURES = {
     "nkv_merge_records_dev": (_int, [_vp, ctypes.POINTER(NkvRun), _int, _vp, _u64, _vp, _vp, _u64p, _u64p]),
     "nkv_merge_records": (_int, [_vp, ctypes.POINTER(_vp), _u64p, ctypes.POINTER(_vp), _u64p, _int, _vp, _u64, _vp,
                                  _u64p, _u64p]),
+    "nkv_summary_entries": (_u64, [_u64, _u64]),
+    "nkv_index_summary_dev": (_int, [_vp, _vp, _u64, _vp, _u64, _u64, _vp, _u64, _vp, _u64, _u64p, _u64p]),
+    "nkv_index_summary_from_records": (_int, [_vp, _vp, _u64, _vp, _u64, _u64, _vp, _u64, _vp, _u64, _u64p,
+                                              _u64p]),
     "nkv_ctx_clock": (_int, [_vp, ctypes.POINTER(ctypes.c_double), _u64p]),
     "nkv_ctx_last_host_timing": (_int, [_vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float),
                                         ctypes.POINTER(ctypes.c_float)]),

@@ -154,7 +154,7 @@ def merge(tables: Sequence[Table], device=None) -> Table:
 
 
 def compact(tables: Sequence[Table], device=None, seed: Optional[int] = None,
-            false_positive_rate: float = 0.01) -> dict:
+            false_positive_rate: float = 0.01, summary_page_size: Optional[int] = None) -> dict:
     """One compaction on the device, the runs uploaded once: every input
     record's Crc checked (nkv_tree_verify_records_dev; a bad one raises
     record.verify's "Bad Record checksum" ValueError before any merge is
@@ -165,11 +165,13 @@ def compact(tables: Sequence[Table], device=None, seed: Optional[int] = None,
 
     Returns {"table": (stream, RecSize array), "root": 20 bytes, "image":
     bytes, "filter": BloomFilter or None, "sources": (run << 32) | index of
-    every output record}.  A merge of no records raises MerkleTreeError, as New
-    does on zero leaves."""
+    every output record}.  With `summary_page_size` the dict also holds "index"
+    and "summary": the merged table's Index and Summary files
+    (nkv_index_summary_dev over the merged table where it lies).  A merge of no
+    records raises MerkleTreeError, as New does on zero leaves."""
     import ctypes
     import torch
-    from . import _lib, bloomfilter
+    from . import _lib, bloomfilter, sstable
     from .merkletree import MerkleTreeError
     _check_runs(tables)
     k = len(tables)
@@ -233,6 +235,10 @@ def compact(tables: Sequence[Table], device=None, seed: Optional[int] = None,
             _lib.check(L.nkv_bloom_insert_records_dev(ctx.h, d_out.data_ptr(), nbytes, d_out_off.data_ptr(), n,
                                                       bf.M, bf.K, bf.HashSeeds[0] if bf.K else 0,
                                                       d_bits.data_ptr()), "compaction filter")
+        d_index = d_summary = None
+        if summary_page_size is not None:
+            d_index, d_summary = sstable.index_summary_dev(ctx, dev, d_out.data_ptr(), nbytes, d_out_off.data_ptr(),
+                                                           n, summary_page_size)
         stream.synchronize()
     if int(d_err.cpu().numpy().view(np.uint32)[0]):
         raise _lib.NkvError(_lib.NKV_ERR_INVALID, "compaction Merkle step")
@@ -242,8 +248,12 @@ def compact(tables: Sequence[Table], device=None, seed: Optional[int] = None,
     root_at = (L.nkv_total_nodes(n) - 1) * 20
     if bf is not None:
         bf._contents = bytearray(d_bits.cpu().numpy()[:(bf.M + 7) // 8].tobytes())
-    return {"table": (d_out.cpu().numpy()[:nbytes].tobytes(), sizes),
-            "root": nodes[root_at:root_at + 20].tobytes(),
-            "image": d_img.cpu().numpy()[:L.nkv_bfs_size(n)].tobytes(),
-            "filter": bf,
-            "sources": d_out_src.cpu().numpy().view(np.uint64)[:n].copy()}
+    out = {"table": (d_out.cpu().numpy()[:nbytes].tobytes(), sizes),
+           "root": nodes[root_at:root_at + 20].tobytes(),
+           "image": d_img.cpu().numpy()[:L.nkv_bfs_size(n)].tobytes(),
+           "filter": bf,
+           "sources": d_out_src.cpu().numpy().view(np.uint64)[:n].copy()}
+    if d_index is not None:
+        out["index"] = d_index.cpu().numpy().tobytes()
+        out["summary"] = d_summary.cpu().numpy().tobytes()
+    return out

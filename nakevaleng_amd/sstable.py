@@ -1,4 +1,4 @@
-"""The Merkle step of the SSTable writer (core/sstable/sstable.go), on the MI355X.
+"""The secondary files of the SSTable writer (core/sstable/sstable.go), on the MI355X.
 
   make_metadata              sstable.makeMetadata           sstable.go:58-74
   make_table_secondaries     Merkle part of MakeTableSecondaries   sstable.go:35-47
@@ -6,10 +6,15 @@
                              serialized Data table
   make_filter_contents       the bits of sstable.makeFilter  sstable.go:49-56 (8f row 4)
   make_filter_from_records   the same over the keys of a serialized Data table
+  index_and_summary          the bytes of sstable.makeIndexAndSummary  sstable.go:76-139
+  make_index_and_summary_from_records   the same into the two files
+  make_table_secondaries_from_records   MakeTableSecondaries over a serialized
+                             Data table: Index, Summary and Metadata files
+                             (and the filter's bits) from one upload
   table_filename             util/filename.Table             filename.go:58-65, 300-309
 
-Everything else the writer produces (Data, Index, Summary files; the Filter's
-gob encoding) is outside this path and unchanged.
+What remains outside this path is the Data file itself and the Filter's gob
+encoding.
 """
 from __future__ import annotations
 
@@ -22,6 +27,8 @@ from .merkletree import MerkleNode, MerkleTree, MerkleTreeError, New, NewLeaf
 from .record import Record
 
 TYPE_METADATA = "metadata"
+TYPE_INDEX = "index"      # filename.go: TypeIndex
+TYPE_SUMMARY = "summary"  # filename.go: TypeSummary
 
 
 def table_filename(path: str, dbname: str, level: int, run: int, filetype: str = TYPE_METADATA) -> str:
@@ -100,3 +107,135 @@ def make_filter_from_records(stream, rec_sizes, seed: int, false_positive_rate: 
                                                  _lib.p8(bits)))
     bf._contents = bytearray(bits.tobytes())
     return bf
+
+
+# ---------------------------------------------------------------------------
+# Index and Summary tables (nkv_index_summary_dev / nkv_index_summary_from_records)
+
+def index_and_summary(stream, rec_sizes, summary_page_size: int, device: Optional[int] = None):
+    """The bytes sstable.makeIndexAndSummary (sstable.go:76-139) writes for the
+    Data table `stream` with KeyContext.RecSize list `rec_sizes`, built on
+    `device` (None: the process's device): (Index file bytes, Summary file
+    bytes).  A summary_page_size of 0 with two or more records raises, where
+    the reference panics on its division."""
+    import ctypes
+    L = _lib.lib()
+    ctx = _lib.default_context(device)
+    buf = np.frombuffer(bytes(stream) + b"\0", dtype=np.uint8)
+    rs = np.ascontiguousarray(rec_sizes, dtype=np.uint64)
+    n, nbytes = int(rs.size), buf.size - 1
+    rs_p = rs if n else np.zeros(1, np.uint64)
+    # enough for a well-formed table (include/nkv_merkle.h); a table whose
+    # KeySize fields reach into later records reports what it needs instead
+    icap = max(nbytes - 14 * n, 0)
+    scap = 24 + 2 * max(nbytes - 30 * n, 0) + icap  # header: two keys; entries: a subset of the Index's
+    ilen, slen = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    for _ in range(2):
+        index, summary = np.empty(icap + 1, np.uint8), np.empty(scap + 1, np.uint8)
+        rc = L.nkv_index_summary_from_records(ctx.h, buf.ctypes.data, nbytes, rs_p.ctypes.data, n,
+                                              int(summary_page_size), index.ctypes.data, icap, summary.ctypes.data,
+                                              scap, ctypes.byref(ilen), ctypes.byref(slen))
+        if rc != _lib.NKV_ERR_INVALID or (ilen.value <= icap and slen.value <= scap):
+            break
+        icap, scap = ilen.value, slen.value
+    _lib.check(rc, "makeIndexAndSummary")
+    return index[:ilen.value].tobytes(), summary[:slen.value].tobytes()
+
+
+def _create(fname: str, data: bytes) -> None:
+    """os.Create + write (sstable.go:80-83): unlike Serialize's metadata file,
+    these two are truncated."""
+    with open(fname, "wb") as f:
+        f.write(data)
+
+
+def make_index_and_summary_from_records(path: str, dbname: str, summary_page_size: int, level: int, run: int,
+                                        stream, rec_sizes, device: Optional[int] = None) -> None:
+    """makeIndexAndSummary's two files, <dbname>-<level>-<run>-index.db and
+    -summary.db, from the Data-table bytes."""
+    f_index = table_filename(path, dbname, level, run, TYPE_INDEX)
+    f_summary = table_filename(path, dbname, level, run, TYPE_SUMMARY)
+    index, summary = index_and_summary(stream, rec_sizes, summary_page_size, device)
+    _create(f_index, index)
+    _create(f_summary, summary)
+
+
+def index_summary_dev(ctx, dev, d_stream: int, nbytes: int, d_rec_off: int, n: int, summary_page_size: int):
+    """nkv_index_summary_dev over a device-resident Data table (addresses as
+    ints): a size query, then the images into two torch tensors of exactly
+    those lengths on `dev`.  Returns (index tensor, summary tensor); they are
+    complete in the order of the context's stream."""
+    import ctypes
+    import torch
+    L = _lib.lib()
+    ilen, slen = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    _lib.check(L.nkv_index_summary_dev(ctx.h, d_stream, nbytes, d_rec_off, n, int(summary_page_size), None, 0, None,
+                                       0, ctypes.byref(ilen), ctypes.byref(slen)), "makeIndexAndSummary")
+    d_index = torch.empty(max(ilen.value, 16), dtype=torch.uint8, device=dev)
+    d_summary = torch.empty(max(slen.value, 16), dtype=torch.uint8, device=dev)
+    _lib.check(L.nkv_index_summary_dev(ctx.h, d_stream, nbytes, d_rec_off, n, int(summary_page_size),
+                                       d_index.data_ptr(), ilen.value, d_summary.data_ptr(), slen.value,
+                                       ctypes.byref(ilen), ctypes.byref(slen)), "makeIndexAndSummary")
+    return d_index[:ilen.value], d_summary[:slen.value]
+
+
+def make_table_secondaries_from_records(path: str, dbname: str, summary_page_size: int, level: int, run: int,
+                                        stream, rec_sizes, device: Optional[int] = None,
+                                        seed: Optional[int] = None, false_positive_rate: float = 0.01):
+    """sstable.MakeTableSecondaries (sstable.go:35-47) over a serialized Data
+    table, uploaded once: the Index and Summary files (truncated, os.Create),
+    the filter's bits when `seed` is given (the gob file is the caller's), and
+    the Metadata file (no O_TRUNC, as Serialize).  Returns (root digest, filter
+    or None).  As in the reference, a table of no records leaves an empty Index
+    and a 24-byte Summary behind before New's error is raised."""
+    import torch
+    from . import bloomfilter, lsmtree
+    L = _lib.lib()
+    dev_index = lsmtree.rank_device(device)
+    ctx = _lib.default_context(dev_index)
+    dev = torch.device("cuda", dev_index)
+    f_index = table_filename(path, dbname, level, run, TYPE_INDEX)
+    f_summary = table_filename(path, dbname, level, run, TYPE_SUMMARY)
+    f_meta = table_filename(path, dbname, level, run)
+    sizes = np.ascontiguousarray(rec_sizes, dtype=np.uint64)
+    data = np.frombuffer(bytes(stream), np.uint8)
+    n, nbytes = int(sizes.size), int(data.size)
+    if n == 0:
+        index, summary = index_and_summary(stream, sizes, summary_page_size, dev_index)
+        _create(f_index, index)
+        _create(f_summary, summary)
+        raise MerkleTreeError("cannot build Merkle Tree from 0 nodes")
+
+    def u8(count):
+        return torch.zeros(max(int(count), 16), dtype=torch.uint8, device=dev)
+
+    ts = torch.cuda.current_stream(dev)
+    with ctx.on_stream(ts.cuda_stream):
+        d_data = torch.from_numpy(data.copy()).to(dev)
+        d_size = torch.from_numpy(sizes.view(np.uint8).copy()).to(dev)
+        d_off = u8(8 * n)
+        _lib.check(L.nkv_record_offsets_dev(ctx.h, d_size.data_ptr(), n, d_off.data_ptr()))
+        d_index, d_summary = index_summary_dev(ctx, dev, d_data.data_ptr(), nbytes, d_off.data_ptr(), n,
+                                               summary_page_size)
+        bf = d_bits = None
+        if seed is not None:
+            bf = bloomfilter.New(n, false_positive_rate, seed=seed, ctx=ctx)
+            d_bits = u8(((bf.M + 31) // 32) * 4)
+            _lib.check(L.nkv_bloom_insert_records_dev(ctx.h, d_data.data_ptr(), nbytes, d_off.data_ptr(), n, bf.M,
+                                                      bf.K, bf.HashSeeds[0] if bf.K else 0, d_bits.data_ptr()),
+                       "makeFilter")
+        d_nodes, d_img, d_err = u8(L.nkv_total_nodes(n) * 20), u8(L.nkv_bfs_size(n)), u8(4)
+        _lib.check(L.nkv_tree_from_records_dev(ctx.h, d_data.data_ptr(), nbytes, d_off.data_ptr(), n,
+                                               d_nodes.data_ptr(), d_err.data_ptr()), "MakeTable")
+        _lib.check(L.nkv_bfs_image_dev(ctx.h, d_nodes.data_ptr(), n, d_img.data_ptr()), "Serialize image")
+        ts.synchronize()
+    if int(d_err.cpu().numpy().view(np.uint32)[0]):
+        raise _lib.NkvError(_lib.NKV_ERR_INVALID, "MakeTable")
+    _create(f_index, d_index.cpu().numpy().tobytes())
+    _create(f_summary, d_summary.cpu().numpy().tobytes())
+    if bf is not None:
+        bf._contents = bytearray(d_bits.cpu().numpy()[:(bf.M + 7) // 8].tobytes())
+    img = np.ascontiguousarray(d_img.cpu().numpy()[:L.nkv_bfs_size(n)])
+    _lib.check(L.nkv_write_file(f_meta.encode(), _lib.p8(img), img.size), f"Serialize({f_meta})")
+    root_at = (L.nkv_total_nodes(n) - 1) * 20
+    return d_nodes.cpu().numpy()[root_at:root_at + 20].tobytes(), bf
