@@ -71,6 +71,9 @@
  *     *index_len and *summary_len bytes.  Inputs are never written:
  *     values, record streams, offset and length arrays and the merge's runs
  *     are read in place (at any alignment where they are bytes).
+ *   - Offsets, strides and stream lengths are full 64-bit quantities: the
+ *     values, spans or records of one call may lie any distance apart inside
+ *     mapped device memory.
  *   - Thread safety: distinct contexts may be used concurrently; one context
  *     must not be used by two threads at once.  Every call re-binds the
  *     context's device (cgo calls may land on any OS thread).

@@ -572,19 +572,20 @@ __device__ __forceinline__ void ring_vc_blocks(uint8_t* wbuf, const uint8_t* p, 
         lastk[k] = 64u * ((nj ? nj : wb_nfull) - 1u);
     }
     const uint8_t* base = reinterpret_cast<const uint8_t*>(wb);
-    const bool near = __all(relk[0] + lastk[0] <= 0xFFFFFFFFull && relk[1] + lastk[1] <= 0xFFFFFFFFull &&
-                            relk[2] + lastk[2] <= 0xFFFFFFFFull && relk[3] + lastk[3] <= 0xFFFFFFFFull);
-    uint32_t rel[4], lastabs[4];
+    // near: every 16-byte request ends inside the descriptor's 0xFFFFFFFF bytes
+    // (one that reaches past them is out of range and delivers zeros)
+    const bool near = __all(relk[0] + lastk[0] + 16ull <= 0xFFFFFFFFull && relk[1] + lastk[1] + 16ull <= 0xFFFFFFFFull &&
+                            relk[2] + lastk[2] + 16ull <= 0xFFFFFFFFull && relk[3] + lastk[3] + 16ull <= 0xFFFFFFFFull);
+    uint32_t rel[4];
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        rel[k] = uint32_t(relk[k]);
-        lastabs[k] = uint32_t(relk[k]) + lastk[k];
-    }
+    for (int k = 0; k < 4; ++k) rel[k] = uint32_t(relk[k]);
     // Chunk c: while every live value still has block c (c < minfull) the
     // offsets are the per-role constants rel[k] from the uniform base + 64 c
     // (saddr-form DMA, no VALU); past that, each role clamps to its value's
-    // last full block (a lane past its value re-reads it).  Waves whose values
-    // lie more than 4 GiB apart take 64-bit addresses throughout.
+    // last full block (a lane past its value re-reads it; rel + min(64 c, last)
+    // stays below the near bound, where rel + 64 c could wrap).  Waves whose
+    // values lie more than 4 GiB apart take 64-bit addresses throughout
+    // (tests/test_gpu_far.py holds both sides of the bound).
     // buffer descriptor over [wb, wb + 4 GiB): the uniform chunk offset rides
     // in soffset, so the in-range issue has no VALU at all
     const __amdgpu_buffer_rsrc_t rsrc =
@@ -603,7 +604,7 @@ __device__ __forceinline__ void ring_vc_blocks(uint8_t* wbuf, const uint8_t* p, 
             for (int k = 0; k < 4; ++k)
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(
                     rsrc, (__attribute__((address_space(3))) void*)(dst + 1024 * k), 16,
-                    min(rel[k] + cb, lastabs[k]), 0, 0, 0);
+                    rel[k] + min(cb, lastk[k]), 0, 0, 0);  // at most rel + last: no 32-bit wrap
         } else {
 #pragma unroll
             for (int k = 0; k < 4; ++k)
@@ -1095,19 +1096,21 @@ __global__ __launch_bounds__(kBlock, LOAD == 4 ? kRunsWaves : kLeafWavesPerSimd)
         if (staged) {
             // done (wave-uniform)
         } else if (MODE == 0) {
-            // value j of this wave at wave_base + j * stride (32-bit offsets:
-            // saddr-form DMA, one VGPR of addressing)
+            // value j of this wave at wave_base + j * stride.  Only a wave that
+            // spans more than 4 GiB gets here (equal block counts: the window
+            // stage refuses nothing else), so every offset is 64-bit: one
+            // pointer per lane, the role's and the block's steps wave-uniform
             const uint64_t first = g * kBlock + 64 * uint64_t(wave);
             const uint8_t* wave_base = base + first * stride;
             const uint32_t nvalid = first < n ? uint32_t(min(uint64_t(64), n - first)) : 0u;
-            const uint32_t off0 = uint32_t(lane >> 2) * uint32_t(stride) + 16u * q;
-            const uint32_t kstep = 16u * uint32_t(stride);
+            const uint8_t* src0 = wave_base + (uint64_t(lane >> 2) * stride + 16u * q);
+            const uint64_t kstep = 16ull * stride;
             const uint32_t nmax = nvalid ? uint32_t(L >> 6) : 0u;
             auto issue = [&](uint32_t b) {
 #pragma unroll
                 for (int k = 0; k < 4; ++k)
                     if (uint32_t(16 * k + (lane >> 2)) < nvalid)
-                        __builtin_amdgcn_global_load_lds(wave_base + (off0 + k * kstep + 64u * b),
+                        __builtin_amdgcn_global_load_lds(src0 + (uint64_t(k) * kstep + 64ull * b),
                                                          wbuf + 1024 * k, 16, 0, 0);
             };
             sha1_blocks_lds(wbuf, nmax, my_nfull, issue, h);
