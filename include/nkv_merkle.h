@@ -34,6 +34,9 @@
  *     over Key ++ Value                                         nkv_crc32_dev
  *   makeIndexAndSummary     core/sstable/sstable.go:76-139      nkv_index_summary_dev /
  *                                                               nkv_index_summary_from_records
+ *   CoreEngine.get, disk    engine/coreeng/coreeng.go:99-160    nkv_lookup_dev /
+ *     path (Filter.Query, FindSummaryTableEntry,                  nkv_lookup_values_dev
+ *     FindIndexTableEntry, record.Deserialize per table)
  *
  * Conventions
  *   - Every function returns an nkv_status (0 = NKV_OK) unless noted; nothing
@@ -58,19 +61,23 @@
  *     offset arrays next to each other in one allocation).
  *       byte strings, at any address: d_img, nkv_bloom_query_dev's d_out, the
  *         buffer of nkv_fill_splitmix64_dev, the merge's d_out, d_index and
- *         d_summary of nkv_index_summary_dev;
+ *         d_summary of nkv_index_summary_dev, d_status and d_stage of
+ *         nkv_lookup_dev, d_out of nkv_lookup_values_dev;
  *       digest arrays (d_nodes, nkv_table.nodes, d_roots and d_out entries of
  *         the group calls), 4-byte aligned: level starts inside a nodes buffer
  *         are multiples of 20 bytes, no more;
  *       uint32_t arrays and filter words (d_crc, d_err, d_bits), 4-byte aligned;
  *       uint64_t arrays (d_rec_off, d_voff, d_vlen, d_stats, d_out_off,
- *         d_out_src), 8-byte aligned.
+ *         d_out_src, d_hit), 8-byte aligned.
  *     nkv_leaf_hash*_dev write level 0 only (20 n bytes); nkv_tree_reduce_dev
  *     leaves level 0 as given; d_bits is ((m + 31) / 32) * 4 bytes; the merge
  *     writes out_len bytes and n_out entries; nkv_index_summary_dev writes
- *     *index_len and *summary_len bytes.  Inputs are never written:
- *     values, record streams, offset and length arrays and the merge's runs
- *     are read in place (at any alignment where they are bytes).
+ *     *index_len and *summary_len bytes; nkv_lookup_dev writes q entries of
+ *     d_hit and d_status and q T bytes of d_stage; nkv_lookup_values_dev
+ *     writes *out_len bytes and q + 1 entries of d_out_off.  Inputs are never
+ *     written: values, record streams, offset and length arrays, the merge's
+ *     runs, and the lookup's tables, filters and query keys are read in place
+ *     (at any alignment where they are bytes).
  *   - Offsets, strides and stream lengths are full 64-bit quantities: the
  *     values, spans or records of one call may lie any distance apart inside
  *     mapped device memory.
@@ -533,6 +540,87 @@ int nkv_index_summary_from_records(nkv_ctx *ctx, const uint8_t *stream, uint64_t
                                    const uint64_t *rec_size, uint64_t n, uint64_t page_size,
                                    uint8_t *index_out, uint64_t index_cap, uint8_t *summary_out,
                                    uint64_t summary_cap, uint64_t *index_len, uint64_t *summary_len);
+
+/* ---- point lookup (engine/coreeng/coreeng.go:99-160, the disk part of get) ----
+ * A batch of q keys looked up in T device-resident tables.  The reference
+ * walks the tables in search order (levels ascending, runs descending: the
+ * caller lists them that way) and per table runs Filter.Query, then
+ * FindSummaryTableEntry, then FindIndexTableEntry, then record.Deserialize at
+ * the Data offset; the first table that holds the key answers, even with a
+ * tombstone.  Over a resident Data table the two Find steps have a closed form
+ * (tests/lookup_ref.py holds it to a literal restatement): with keys K_0 <
+ * ... < K_(n-1) compared as bytes.Compare does (unsigned, a proper prefix
+ * sorts first), FindSummaryTableEntry gives Offset -1 exactly when key < K_0
+ * or key > K_(n-1), and FindIndexTableEntry exactly when no K_j equals the
+ * key.  The tables' keys are assumed strictly increasing -- what the merge
+ * validates and writes; this call does not check it again.
+ *
+ * A table is its Data table (stream, rec_off as for nkv_tree_from_records_dev)
+ * and, optionally, its filter: bits = the words nkv_bloom_insert[_records]_dev
+ * leaves (((m + 31) / 32) * 4 bytes, 4-byte aligned) with its m, k and first
+ * seed.  bits NULL: no filter, every key passes.  A filter that rejects a key
+ * its table in fact holds makes that table report FILTER and the search move
+ * on, exactly as the reference would. */
+#define NKV_LOOKUP_MAX_TABLES 32
+typedef struct nkv_lookup_table { /* all pointers on the context's device */
+    const void *stream;      /* Data table, as for nkv_tree_from_records_dev */
+    uint64_t stream_len;
+    const uint64_t *rec_off; /* n record offsets */
+    uint64_t n;              /* >= 1 */
+    const void *bits;        /* filter words as nkv_bloom_insert_dev leaves them; NULL = no filter, every key passes */
+    uint32_t m, k, seed0;
+} nkv_lookup_table;
+
+#define NKV_STAGE_NOT_SEARCHED 0 /* an earlier table answered */
+#define NKV_STAGE_FILTER 1       /* Filter.Query said no */
+#define NKV_STAGE_SUMMARY 2      /* key < K_0 or key > K_(n-1): FindSummaryTableEntry's Offset -1 */
+#define NKV_STAGE_INDEX 3        /* in range, no equal key: FindIndexTableEntry's Offset -1 */
+#define NKV_STAGE_FOUND 4
+#define NKV_GET_ABSENT 0
+#define NKV_GET_LIVE 1
+#define NKV_GET_TOMBSTONE 2      /* found, Status & 1: the engine answers "not found" and stops */
+
+/* Asynchronous on the context's stream.  Query i is the d_klen[i] bytes at
+ * d_keys + d_koff[i], at any alignment; the empty key and duplicate queries are
+ * allowed.  d_hit[i] = (table << 32) | record index of the first table, in the
+ * order given, whose search ends FOUND, UINT64_MAX if none does; d_status[i]
+ * one of the NKV_GET codes; d_stage (nullable, q * T bytes): d_stage[i * T + t]
+ * the NKV_STAGE at which table t's search for query i ended.
+ *
+ * d_err (nullable, one uint32_t, need not be initialised) receives 1 if a
+ * probed record's header or key span reaches outside its stream, else 0.  Such
+ * a probe counts as "no match" (its table's search ends at INDEX) and nothing
+ * outside the stream is read.  With d_err NULL the call synchronizes and
+ * returns NKV_ERR_INVALID in that case.  Also NKV_ERR_INVALID, with nothing
+ * launched: T outside 1..NKV_LOOKUP_MAX_TABLES, a table with n = 0 (the
+ * reference cannot write one: New panics on zero leaves) or a NULL stream or
+ * rec_off, a filter with k > 0 and m = 0, n or q above 2^31 - 1, a NULL
+ * required pointer.  q = 0 returns NKV_OK and writes nothing.
+ *
+ * The found record's stored Crc is not checked (record.Deserialize does,
+ * record.go:163-169): a caller who wants that runs nkv_record_crc_dev over the
+ * table. */
+int nkv_lookup_dev(nkv_ctx *ctx, const nkv_lookup_table *tables, int T, const void *d_keys,
+                   const uint64_t *d_koff, const uint64_t *d_klen, uint64_t q, uint64_t *d_hit,
+                   uint8_t *d_status, uint8_t *d_stage, uint32_t *d_err);
+/* The Values of the LIVE hits, packed in query order: Value i is
+ * d_out[d_out_off[i] .. d_out_off[i + 1]), and a query whose status is ABSENT
+ * or TOMBSTONE contributes 0 bytes.  d_hit / d_status / tables as the lookup
+ * took and left them.  d_out_off holds q + 1 entries; d_out may sit at any byte
+ * alignment, and exactly *out_len (host) bytes of it are written.  With d_out
+ * NULL the call is a size query (d_out_off may be NULL too): NKV_OK and the
+ * length.  A kernel checks every hit's Value span against its stream first and
+ * the host reads its verdict and the length once (the call's one synchronize)
+ * before anything is written: NKV_ERR_INVALID, and nothing written, for a hit
+ * that names no record or whose Value reaches outside its stream (length 0),
+ * and for out_cap < *out_len (the length still reported, so the caller can
+ * retry).  q = 0 gives *out_len = 0 and d_out_off[0] = 0.  Under
+ * NKV_TIMING_EVENTS the "leaf" interval is the measure kernel, the scan and
+ * the host's read of the length, the "reduce" interval the copy of the offsets
+ * and the copy kernel. */
+int nkv_lookup_values_dev(nkv_ctx *ctx, const nkv_lookup_table *tables, int T, const uint64_t *d_hit,
+                          const uint8_t *d_status, uint64_t q, void *d_out, uint64_t out_cap,
+                          uint64_t *d_out_off, uint64_t *out_len);
 
 /* ---- several tables per call (compaction's runs, consecutive flushes) ----
  * One table of device-resident leaves, described for nkv_trees_dev /

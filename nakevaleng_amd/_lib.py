@@ -79,7 +79,23 @@ class NkvRun(ctypes.Structure):
     _fields_ = [("stream", _vp), ("stream_len", _u64), ("rec_off", _vp), ("n", _u64)]
 
 
+class NkvLookupTable(ctypes.Structure):
+    """struct nkv_lookup_table: one device-resident table of nkv_lookup_dev (bits None = no filter)."""
+    _fields_ = [("stream", _vp), ("stream_len", _u64), ("rec_off", _vp), ("n", _u64), ("bits", _vp),
+                ("m", ctypes.c_uint32), ("k", ctypes.c_uint32), ("seed0", ctypes.c_uint32)]
+
+
 NKV_MERGE_MAX_RUNS = 16
+NKV_LOOKUP_MAX_TABLES = 32
+NKV_STAGE_NOT_SEARCHED = 0
+NKV_STAGE_FILTER = 1
+NKV_STAGE_SUMMARY = 2
+NKV_STAGE_INDEX = 3
+NKV_STAGE_FOUND = 4
+NKV_GET_ABSENT = 0
+NKV_GET_LIVE = 1
+NKV_GET_TOMBSTONE = 2
+NKV_HIT_NONE = 2**64 - 1  # d_hit of a key no table holds
 INDEX_WRITE_TILE = 16384  # csrc/index.hip kWriteTile: image bytes one writer workgroup owns
 _tabp = ctypes.POINTER(NkvTable)
 
@@ -150,6 +166,9 @@ SIGNATURES = {
     "nkv_index_summary_dev": (_int, [_vp, _vp, _u64, _vp, _u64, _u64, _vp, _u64, _vp, _u64, _u64p, _u64p]),
     "nkv_index_summary_from_records": (_int, [_vp, _vp, _u64, _vp, _u64, _u64, _vp, _u64, _vp, _u64, _u64p,
                                               _u64p]),
+    "nkv_lookup_dev": (_int, [_vp, ctypes.POINTER(NkvLookupTable), _int, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp]),
+    "nkv_lookup_values_dev": (_int, [_vp, ctypes.POINTER(NkvLookupTable), _int, _vp, _vp, _u64, _vp, _u64, _vp,
+                                     _u64p]),
     "nkv_ctx_clock": (_int, [_vp, ctypes.POINTER(ctypes.c_double), _u64p]),
     "nkv_ctx_last_host_timing": (_int, [_vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float),
                                         ctypes.POINTER(ctypes.c_float)]),

@@ -19,69 +19,17 @@
 #include <stdint.h>
 
 #include "internal.hpp"
+#include "murmur_dev.hpp"  // mm_states, mm_fmix, fastmod_u32, kBloomMaxK
 
 namespace nkv {
 
 constexpr int kBloomBlock = 256;
-constexpr int kBloomMaxK = 16;
-
-__device__ __forceinline__ uint32_t mm_rotl(uint32_t x, int r) { return (x << r) | (x >> (32 - r)); }
-
-__device__ __forceinline__ uint32_t mm_fmix(uint32_t h) {
-    h ^= h >> 16;
-    h *= 0x85ebca6bu;
-    h ^= h >> 13;
-    h *= 0xc2b2ae35u;
-    h ^= h >> 16;
-    return h;
-}
-
-__device__ __forceinline__ uint32_t mm_block(uint32_t k) {
-    k *= 0xcc9e2d51u;
-    k = mm_rotl(k, 15);
-    return k * 0x1b873593u;
-}
-
-// Lemire fastmod: a % d with M = 2^64 / d rounded up (M = 0 for d = 1).
-__device__ __forceinline__ uint32_t fastmod_u32(uint32_t a, uint64_t M, uint32_t d) {
-    const uint64_t low = M * a;
-    return uint32_t(__umul64hi(low, uint64_t(d)));
-}
 
 __device__ __forceinline__ uint64_t bl_ld_le64(const uint8_t* p) {
     uint64_t v = 0;
 #pragma unroll
     for (int i = 0; i < 8; ++i) v |= uint64_t(p[i]) << (8 * i);
     return v;
-}
-
-// h[j] = MurmurHash3_x86_32(key, seed0 + j0 + j) before the final length xor
-// and fmix, for j < nk (<= kBloomMaxK).
-__device__ __forceinline__ void mm_states(const uint8_t* key, uint64_t len, uint32_t seed, int nk,
-                                          uint32_t h[kBloomMaxK]) {
-#pragma unroll
-    for (int j = 0; j < kBloomMaxK; ++j) h[j] = seed + uint32_t(j);
-    const uint32_t s = uint32_t(reinterpret_cast<uintptr_t>(key)) & 3u;
-    const uint32_t* q = reinterpret_cast<const uint32_t*>(key - s);  // stays a global pointer
-    const uint64_t nb = len >> 2;
-    const uint32_t nxt = s != 0u;  // the dword after q[i] holds key bytes only when s > 0
-    for (uint64_t i = 0; i < nb; ++i) {
-        const uint32_t k = mm_block(__builtin_amdgcn_alignbyte(q[i + nxt], q[i], s));
-#pragma unroll
-        for (int j = 0; j < kBloomMaxK; ++j)
-            if (j < nk) h[j] = mm_rotl(h[j] ^ k, 13) * 5u + 0xe6546b64u;
-    }
-    const uint32_t r = uint32_t(len & 3u);
-    if (r) {
-        // bytes 4nb .. 4nb+r-1: in q[nb] and, if s + r > 4, q[nb + 1]
-        const uint32_t w0 = q[nb];
-        const uint32_t w1 = s + r > 4u ? q[nb + 1] : w0;
-        const uint32_t t = __builtin_amdgcn_alignbyte(w1, w0, s) & (0xFFFFFFFFu >> (8 * (4 - r)));
-        const uint32_t k = mm_block(t);
-#pragma unroll
-        for (int j = 0; j < kBloomMaxK; ++j)
-            if (j < nk) h[j] ^= k;
-    }
 }
 
 // MODE 0: key i at base + off[i], len[i].  MODE 1: key of the record at
@@ -130,8 +78,6 @@ __global__ __launch_bounds__(kBloomBlock) void k_bloom(const uint8_t* __restrict
     }
     if (QUERY) out[i] = hit ? 1 : 0;
 }
-
-static uint64_t fastmod_magic(uint32_t d) { return ~uint64_t(0) / d + 1; }
 
 // ---------------------------------------------------------------------------
 // Range-privatised insert.  A filter's n*k bit updates land on m bits at

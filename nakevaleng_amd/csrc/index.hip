@@ -27,6 +27,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "bytes_dev.hpp"  // ld_le64, sel4, first_at_least
 #include "context.hpp"
 
 using namespace nkv;
@@ -39,13 +40,6 @@ constexpr uint32_t kWriteTile = 16384;  // image bytes per workgroup
 constexpr uint32_t kWriteChunk = 16;    // image bytes per lane and step
 // entries that can overlap one tile: at most kWriteTile / kEnt + 2 = 1026
 constexpr uint32_t kWriteList = 1032;
-
-__device__ __forceinline__ uint64_t ld_le64(const uint8_t* p) {  // any alignment
-    uint64_t v = 0;
-#pragma unroll
-    for (int b = 0; b < 8; ++b) v |= uint64_t(p[b]) << (8 * b);
-    return v;
-}
 
 // Selected record of Summary entry e (m entries over n records): e * page, the
 // last entry the last record.  The Index is the same with page = 1, m = n.
@@ -93,29 +87,6 @@ struct Image {  // the entries of one image
     const uint64_t* field;  // the Offset field of record i's entry
     uint64_t n, page;       // record_of
 };
-
-__device__ __forceinline__ uint32_t sel4(uint32_t q, uint32_t a, uint32_t b, uint32_t c, uint32_t d) {
-    return q == 0 ? a : (q == 1 ? b : (q == 2 ? c : d));
-}
-
-// The first index in [lo, hi) with a[index] >= key (hi if none), a ascending,
-// found by the whole workgroup: every lane probes one of kBlock evenly spaced
-// places and the count of probes below the key picks the gap between two of
-// them, so a million entries take three dependent loads instead of twenty.
-// lo, hi and key must be the same in every lane; so is the result.
-__device__ __forceinline__ uint64_t first_at_least(const uint64_t* __restrict__ a, uint64_t lo, uint64_t hi,
-                                                   uint64_t key) {
-    while (lo < hi) {
-        const uint64_t step = (hi - lo + kBlock - 1) / kBlock;
-        const uint64_t p = lo + threadIdx.x * step;
-        const int c = __syncthreads_count(p < hi && a[p] < key);  // the probes below the key are the first c
-        if (c == 0) return lo;
-        const uint64_t next = lo + uint64_t(c) * step;  // the first probe not below the key, if it exists
-        lo = lo + uint64_t(c - 1) * step + 1;
-        hi = next < hi ? next : hi;
-    }
-    return lo;
-}
 
 // Image byte o is byte o - eoff[e] of entry e, for the e with eoff[e] <= o <
 // eoff[e + 1]: bytes 0..7 KeySize, 8..15 the Offset field, then the key, which

@@ -1,0 +1,424 @@
+// lookup.hip -- batched point lookup over device-resident SSTables, the disk
+// part of the engine's get (engine/coreeng/coreeng.go:99-160): nkv_lookup_dev /
+// nkv_lookup_values_dev.
+//
+// The reference walks the tables in search order and, per table, runs
+// Filter.Query, FindSummaryTableEntry, FindIndexTableEntry and
+// record.Deserialize, each over a file it re-opens and scans.  Over a resident
+// Data table the Summary and Index steps have a closed form: the Summary
+// refuses a key outside [K_0, K_(n-1)], the Index a key that no record holds.
+//
+//   k_lookup        one lane per query, the tables in order: the filter test is
+//                   mm_states (murmur_dev.hpp) over the query key, the range
+//                   test reads the keys of records 0 and n - 1, and a lower
+//                   bound over rec_off reads every probed key in place.  Keys
+//                   are compared by an 8-byte big-endian prefix first and byte
+//                   by byte only where the prefixes are equal.
+//   k_value_measure one lane per query: the found record's Value span, checked
+//                   against its stream.
+//   scan            exclusive sums of the lengths = the packed offsets; the host
+//                   reads the total and the verdict before the copy is launched.
+//   k_value_copy    tiles the OUTPUT bytes as k_merge_copy does: a workgroup
+//                   owns 16 KiB of d_out and every lane writes 16 destination-
+//                   aligned bytes per step, put together in registers from
+//                   aligned 16-byte loads of the one or more Values that
+//                   overlap them.  Values can be empty, so a tile can
+//                   overlap any number of queries: up to kCopyList of them are
+//                   kept in LDS, more are searched in the offset array itself.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "bytes_dev.hpp"
+#include "context.hpp"
+#include "murmur_dev.hpp"
+
+using namespace nkv;
+
+namespace {
+
+constexpr int kHdr = 30;  // record.go:191-199: Crc 4 | Timestamp 8 | Status 1 | TypeInfo 1 | KeySize 8 | ValueSize 8
+constexpr uint64_t kNone = ~uint64_t(0);
+constexpr uint32_t kCopyTile = 16384;  // output bytes per workgroup
+constexpr uint32_t kCopyChunk = 16;    // output bytes per lane and step
+constexpr uint32_t kCopyList = 1024;   // queries of a tile kept in LDS
+
+struct Tables {  // kernel argument: the T tables in search order
+    const uint8_t* stream[NKV_LOOKUP_MAX_TABLES];
+    uint64_t len[NKV_LOOKUP_MAX_TABLES];
+    const uint64_t* off[NKV_LOOKUP_MAX_TABLES];
+    const uint32_t* bits[NKV_LOOKUP_MAX_TABLES];  // nullptr: every key passes
+    uint64_t M[NKV_LOOKUP_MAX_TABLES];            // fastmod_magic(m)
+    uint32_t n[NKV_LOOKUP_MAX_TABLES], m[NKV_LOOKUP_MAX_TABLES], k[NKV_LOOKUP_MAX_TABLES],
+        seed[NKV_LOOKUP_MAX_TABLES];
+    int T;
+};
+
+struct Query {
+    const uint8_t* key;
+    uint64_t len;
+    uint64_t pfx;  // first 8 key bytes, big-endian, zero-padded
+};
+
+__device__ __forceinline__ uint64_t prefix_of(const uint8_t* key, uint64_t len) {
+    uint64_t p = 0;
+    for (uint32_t b = 0; b < 8 && b < len; ++b) p |= uint64_t(key[b]) << (56 - 8 * b);
+    return p;
+}
+
+constexpr int kBad = 2;  // probe: the record's header or key span leaves the stream
+
+// bytes.Compare(query, key of record j): -1, 0, 1, or kBad.  Nothing outside
+// [s, s + L) is read.
+__device__ __forceinline__ int probe(const Query& Q, const uint8_t* __restrict__ s, uint64_t L,
+                                     const uint64_t* __restrict__ off, uint64_t j) {
+    const uint64_t o = off[j];
+    if (!header_in(o, L)) return kBad;
+    const uint64_t ks = ld_le64(s + o + 14);
+    if (ks > L - o - kHdr) return kBad;
+    const uint8_t* rk = s + o + kHdr;
+    const uint64_t rp = prefix_of(rk, ks);
+    if (Q.pfx != rp) return Q.pfx < rp ? -1 : 1;
+    // equal padded prefixes: a key of at most 8 bytes is a prefix of the other
+    if (Q.len <= 8 || ks <= 8) return Q.len < ks ? -1 : (Q.len > ks ? 1 : 0);
+    return cmp_bytes(Q.key + 8, Q.len - 8, rk + 8, ks - 8);
+}
+
+// Filter.Query (bloomfilter.go:93-111): every one of the k bits set.
+__device__ __forceinline__ bool filter_passes(const Query& Q, const uint32_t* __restrict__ bits, uint32_t m, uint64_t M,
+                                              uint32_t k, uint32_t seed0) {
+    bool hit = true;
+    for (uint32_t j0 = 0; j0 < k && hit; j0 += kBloomMaxK) {
+        const int nk = int(min(k - j0, uint32_t(kBloomMaxK)));
+        uint32_t h[kBloomMaxK];
+        mm_states(Q.key, Q.len, seed0 + j0, nk, h);
+#pragma unroll
+        for (int j = 0; j < kBloomMaxK; ++j) {
+            if (j < nk) {
+                const uint32_t idx = fastmod_u32(mm_fmix(h[j] ^ uint32_t(Q.len)), M, m);
+                hit = hit && ((bits[idx >> 5] >> (idx & 31u)) & 1u);
+            }
+        }
+    }
+    return hit;
+}
+
+// One table's search: the stage it ends at and, when FOUND, the record index.
+// A bad probe ends the search at INDEX (no equal key) and raises *bad.
+__device__ __forceinline__ uint32_t search(const Tables& R, int t, const Query& Q, uint64_t* found, bool* bad) {
+    const uint32_t* bits = R.bits[t];
+    if (bits && !filter_passes(Q, bits, R.m[t], R.M[t], R.k[t], R.seed[t])) return NKV_STAGE_FILTER;
+    const uint8_t* s = R.stream[t];
+    const uint64_t L = R.len[t];
+    const uint64_t* off = R.off[t];
+    const uint64_t n = R.n[t];
+    int c = probe(Q, s, L, off, 0);
+    uint64_t j = 0;
+    if (c < 0) return NKV_STAGE_SUMMARY;  // key < MinKey
+    if (c == 1 && n > 1) {
+        j = n - 1;
+        c = probe(Q, s, L, off, j);
+    }
+    if (c == 1) return NKV_STAGE_SUMMARY;  // key > MaxKey
+    if (c < 0) {  // K_0 < key < K_(n-1): the first record in (0, n - 1) whose key is not below the query's
+        uint64_t lo = 1, hi = n - 1;
+        while (lo < hi) {
+            j = lo + (hi - lo) / 2;
+            c = probe(Q, s, L, off, j);
+            if (c == 1) lo = j + 1;
+            else if (c < 0) hi = j;
+            else break;  // equal, or a bad record
+        }
+    }
+    if (c == kBad) *bad = true;
+    if (c != 0) return NKV_STAGE_INDEX;
+    *found = j;
+    return NKV_STAGE_FOUND;
+}
+
+// Every wave with a query keeps its 64 lanes busy: lanes past q redo the last
+// query and store nothing.
+__global__ __launch_bounds__(kBlock) void k_lookup(Tables R, const uint8_t* __restrict__ keys,
+                                                   const uint64_t* __restrict__ koff,
+                                                   const uint64_t* __restrict__ klen, uint64_t q,
+                                                   uint64_t* __restrict__ hit, uint8_t* __restrict__ status,
+                                                   uint8_t* __restrict__ stage, unsigned int* __restrict__ err) {
+    const uint64_t gi = uint64_t(blockIdx.x) * kBlock + threadIdx.x;
+    if ((gi & ~uint64_t(63)) >= q) return;
+    const bool live = gi < q;
+    const uint64_t i = live ? gi : q - 1;
+    Query Q;
+    Q.key = keys + koff[i];
+    Q.len = klen[i];
+    Q.pfx = prefix_of(Q.key, Q.len);
+    uint64_t h = kNone;
+    uint8_t st = NKV_GET_ABSENT;
+    bool bad = false;
+    for (int t = 0; t < R.T; ++t) {
+        uint32_t sg = NKV_STAGE_NOT_SEARCHED;
+        if (h == kNone) {
+            uint64_t j = 0;
+            sg = search(R, t, Q, &j, &bad);
+            if (sg == NKV_STAGE_FOUND) {
+                h = (uint64_t(t) << 32) | j;
+                st = (R.stream[t][R.off[t][j] + 12] & 1) ? NKV_GET_TOMBSTONE : NKV_GET_LIVE;
+            }
+        }
+        if (stage && live) stage[i * uint64_t(R.T) + t] = uint8_t(sg);
+    }
+    if (live) {
+        hit[i] = h;
+        status[i] = st;
+        if (bad) atomicOr(err, 1u);
+    }
+}
+
+// len[i] / src[i]: the Value of LIVE hit i (0 bytes for every other query)
+__global__ __launch_bounds__(kBlock) void k_value_measure(Tables R, const uint64_t* __restrict__ hit,
+                                                          const uint8_t* __restrict__ status, uint64_t q,
+                                                          uint64_t* __restrict__ len, uint64_t* __restrict__ src,
+                                                          unsigned int* __restrict__ err) {
+    const uint64_t i = uint64_t(blockIdx.x) * kBlock + threadIdx.x;
+    if (i >= q) return;
+    uint64_t vs = 0, at = 0;
+    if (status[i] == NKV_GET_LIVE) {
+        const uint64_t h = hit[i], t = h >> 32, j = h & 0xFFFFFFFFull;
+        bool bad = t >= uint64_t(R.T) || j >= R.n[t < uint64_t(R.T) ? t : 0];
+        if (!bad) {
+            const uint8_t* s = R.stream[t];
+            const uint64_t L = R.len[t], o = R.off[t][j];
+            bad = !header_in(o, L);
+            if (!bad) {
+                const uint64_t ks = ld_le64(s + o + 14), v = ld_le64(s + o + 22), room = L - o - kHdr;
+                if (ks > room || v > room - ks) {
+                    bad = true;
+                } else {
+                    vs = v;
+                    at = uint64_t(reinterpret_cast<uintptr_t>(s + o + kHdr + ks));
+                }
+            }
+        }
+        if (bad) atomicOr(err, 1u);
+    }
+    len[i] = vs;
+    src[i] = at;
+}
+
+// off[q] = the total, next to the error word for the host
+__global__ void k_value_total(const uint64_t* __restrict__ len, uint64_t* __restrict__ off, uint64_t q,
+                              uint64_t* __restrict__ total) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    off[q] = off[q - 1] + len[q - 1];
+    *total = off[q];
+}
+
+// The last index j in [lo, hi) with a[j] <= x; a ascending, a[lo] <= x.
+template <class A>
+__device__ __forceinline__ uint64_t last_at_most(const A& a, uint64_t lo, uint64_t hi, uint64_t x) {
+    while (hi - lo > 1) {
+        const uint64_t mid = lo + (hi - lo) / 2;
+        if (a[mid] <= x) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// Output byte o is byte o - off[i] of the Value at src[i], for the i with
+// off[i] <= o < off[i + 1] (off holds q + 1 entries, equal neighbours where a
+// Value is empty: the last i with off[i] <= o is the one that holds o).  Chunks
+// lie on the 16-byte grid of d_out's address, so every full chunk is one
+// aligned 16-byte store, OR-ed together from the pieces of the Values that
+// overlap it (ld_piece: one or two aligned 16-byte loads per piece, shifted
+// and masked in registers); only the partial chunks at the two ends of the
+// output go byte by byte.
+__global__ __launch_bounds__(kBlock) void k_value_copy(uint8_t* __restrict__ out, const uint64_t* __restrict__ off,
+                                                       const uint64_t* __restrict__ src, uint64_t q,
+                                                       uint64_t out_len) {
+    __shared__ uint64_t l_off[kCopyList + 1];
+    __shared__ uint64_t l_src[kCopyList];
+    const uint64_t head = uint64_t(reinterpret_cast<uintptr_t>(out)) & 15;  // grid position p = o + head
+    const uint64_t p0 = uint64_t(blockIdx.x) * kCopyTile, pend = head + out_len;
+    if (p0 >= pend) return;
+    const uint64_t o_lo = p0 > head ? p0 - head : 0;
+    const uint64_t o_hi = p0 + kCopyTile < pend ? p0 + kCopyTile - head : out_len;  // > o_lo
+    // queries holding bytes of [o_lo, o_hi): from jlo, which holds o_lo, to jhi, which holds o_hi - 1
+    // (found by the whole workgroup: off[0] = 0 <= o_lo, and jhi is the last with off < o_hi)
+    const uint64_t jlo = first_at_least(off, 0, q, o_lo + 1) - 1;
+    const uint64_t jhi = first_at_least(off, jlo + 1, q, o_hi) - 1;
+    const bool listed = jhi - jlo < kCopyList;  // wave-uniform
+    const uint32_t cnt = listed ? uint32_t(jhi - jlo + 1) : 0;
+    for (uint32_t e = threadIdx.x; e < cnt; e += kBlock) {
+        l_off[e] = off[jlo + e];
+        l_src[e] = src[jlo + e];
+    }
+    if (threadIdx.x == 0) l_off[cnt] = off[jhi + 1];
+    __syncthreads();
+#pragma unroll 1
+    for (uint32_t it = 0; it < kCopyTile / (kCopyChunk * kBlock); ++it) {
+        const uint64_t p = p0 + uint64_t(it * kBlock + threadIdx.x) * kCopyChunk;
+        if (p + kCopyChunk <= head || p >= pend) continue;
+        const uint64_t ob = p > head ? p - head : 0;  // first output byte of the chunk
+        const bool whole = p >= head && p + kCopyChunk <= pend;
+        // e = the query that holds ob (index into the list, or jlo + e in the arrays)
+        const uint64_t e0 = listed ? last_at_most(l_off, 0, cnt, ob) : last_at_most(off, jlo, jhi + 1, ob) - jlo;
+        const uint64_t off0 = listed ? l_off[e0] : off[jlo + e0];
+        const uint64_t off1 = listed ? l_off[e0 + 1] : off[jlo + e0 + 1];
+        const uint64_t src0 = listed ? l_src[e0] : src[jlo + e0];
+        uint64_t e = e0, a = off0, b = off1, sa = src0;
+        if (whole) {  // the pieces of the Values that overlap the chunk, one or two loads each
+            uint4 acc = make_uint4(0, 0, 0, 0);
+            const uint64_t oe = ob + kCopyChunk;  // <= o_hi: the queries up to jhi hold it all
+            uint64_t o = ob;
+            for (;;) {
+                const uint64_t hi = b < oe ? b : oe;
+                if (hi > o) {  // bytes [o, hi) are the Value's from o - a on
+                    const uint4 v = ld_piece(sa + (o - a), uint32_t(hi - o), uint32_t(o - ob));
+                    acc.x |= v.x;
+                    acc.y |= v.y;
+                    acc.z |= v.z;
+                    acc.w |= v.w;
+                    o = hi;
+                }
+                if (o >= oe) break;
+                ++e;
+                a = b;
+                b = listed ? l_off[e + 1] : off[jlo + e + 1];
+                sa = listed ? l_src[e] : src[jlo + e];
+            }
+            *reinterpret_cast<uint4*>(out + ob) = acc;
+        } else {  // the two ends of the output: byte by byte
+            for (uint32_t k = 0; k < kCopyChunk; ++k) {
+                const uint64_t pb = p + k;
+                if (pb < head || pb >= pend) continue;
+                const uint64_t o = pb - head;
+                while (o >= b) {  // o < out_len = off[q]: ends at the query that holds o
+                    ++e;
+                    a = b;
+                    b = listed ? l_off[e + 1] : off[jlo + e + 1];
+                    sa = listed ? l_src[e] : src[jlo + e];
+                }
+                out[o] = *reinterpret_cast<const uint8_t*>(uintptr_t(sa + (o - a)));
+            }
+        }
+    }
+}
+
+inline unsigned blocks_for(uint64_t n) { return unsigned((n + kBlock - 1) / kBlock); }
+
+// The tables as the kernels take them; NKV_ERR_INVALID for what the header refuses.
+int pack_tables(const nkv_lookup_table* tables, int T, Tables* R) {
+    if (!tables || T < 1 || T > NKV_LOOKUP_MAX_TABLES) return NKV_ERR_INVALID;
+    *R = Tables{};
+    R->T = T;
+    for (int t = 0; t < T; ++t) {
+        const nkv_lookup_table& u = tables[t];
+        if (u.n < 1 || u.n > kMaxN || !u.stream || !u.rec_off) return NKV_ERR_INVALID;
+        if (u.bits && u.k && u.m == 0) return NKV_ERR_INVALID;
+        R->stream[t] = static_cast<const uint8_t*>(u.stream);
+        R->len[t] = u.stream_len;
+        R->off[t] = u.rec_off;
+        R->n[t] = uint32_t(u.n);
+        const bool filtered = u.bits && u.k;  // k = 0: Query's loop has no bit to miss
+        R->bits[t] = filtered ? static_cast<const uint32_t*>(u.bits) : nullptr;
+        R->m[t] = filtered ? u.m : 1;
+        R->M[t] = fastmod_magic(R->m[t]);
+        R->k[t] = filtered ? u.k : 0;
+        R->seed[t] = u.seed0;
+    }
+    return NKV_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int nkv_lookup_dev(nkv_ctx* c, const nkv_lookup_table* tables, int T, const void* d_keys, const uint64_t* d_koff,
+                   const uint64_t* d_klen, uint64_t q, uint64_t* d_hit, uint8_t* d_status, uint8_t* d_stage,
+                   uint32_t* d_err) try {
+    TRY(bind(c));
+    Tables R;
+    TRY(pack_tables(tables, T, &R));
+    if (q > kMaxN) return NKV_ERR_INVALID;
+    if (q == 0) return NKV_OK;
+    if (!d_keys || !d_koff || !d_klen || !d_hit || !d_status) return NKV_ERR_INVALID;
+    unsigned int* err = d_err;
+    if (!err) {
+        TRY(grow(c->d_stats, 8));
+        err = static_cast<unsigned int*>(c->d_stats.p);
+    }
+    HIPTRY(hipMemsetAsync(err, 0, 4, c->stream));
+    hipLaunchKernelGGL(k_lookup, dim3(blocks_for(q)), dim3(kBlock), 0, c->stream, R,
+                       static_cast<const uint8_t*>(d_keys), d_koff, d_klen, q, d_hit, d_status, d_stage, err);
+    HIPTRY(hipGetLastError());
+    if (d_err) return NKV_OK;
+    unsigned int h_err = 0;
+    HIPTRY(hipMemcpyAsync(&h_err, err, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPTRY(hipStreamSynchronize(c->stream));
+    return h_err ? NKV_ERR_INVALID : NKV_OK;
+} NKV_CATCH
+
+int nkv_lookup_values_dev(nkv_ctx* c, const nkv_lookup_table* tables, int T, const uint64_t* d_hit,
+                          const uint8_t* d_status, uint64_t q, void* d_out, uint64_t out_cap, uint64_t* d_out_off,
+                          uint64_t* out_len) try {
+    TRY(bind(c));
+    if (!out_len) return NKV_ERR_INVALID;
+    *out_len = 0;
+    Tables R;
+    TRY(pack_tables(tables, T, &R));
+    if (q > kMaxN) return NKV_ERR_INVALID;
+    const bool query = !d_out;
+    if (q == 0) {  // no Value: the one offset entry is 0
+        if (!query && d_out_off) HIPTRY(hipMemsetAsync(d_out_off, 0, 8, c->stream));
+        return NKV_OK;
+    }
+    if (!d_hit || !d_status || (!query && !d_out_off)) return NKV_ERR_INVALID;
+
+    // scratch in d_stmp, which carries nothing from call to call: the lengths
+    // (q), their exclusive sums (q + 1) and the Values' addresses (q)
+    TRY(grow(c->d_stmp, 8 * (3 * q + 1)));
+    uint64_t* a = static_cast<uint64_t*>(c->d_stmp.p);
+    uint64_t *len = a, *off = a + q, *src = a + 2 * q + 1;
+    size_t tb = 0;
+    HIPTRY(scan_exclusive_u64(len, off, q, nullptr, &tb, c->stream));
+    TRY(grow(c->d_tmp, tb));
+    TRY(grow(c->d_stats, 16));  // [err | total]
+    unsigned int* err = static_cast<unsigned int*>(c->d_stats.p);
+    uint64_t* total = static_cast<uint64_t*>(c->d_stats.p) + 1;
+
+    // with NKV_TIMING_EVENTS: "leaf" = measure, scan and the host's read of the
+    // length, "reduce" = the offsets' copy and the copy kernel
+    TRY(mark(c, 0));
+    HIPTRY(hipMemsetAsync(err, 0, 16, c->stream));
+    hipLaunchKernelGGL(k_value_measure, dim3(blocks_for(q)), dim3(kBlock), 0, c->stream, R, d_hit, d_status, q, len,
+                       src, err);
+    HIPTRY(hipGetLastError());
+    HIPTRY(scan_exclusive_u64(len, off, q, c->d_tmp.p, &tb, c->stream));
+    hipLaunchKernelGGL(k_value_total, dim3(1), dim3(1), 0, c->stream, len, off, q, total);
+    HIPTRY(hipGetLastError());
+    // the verdict and the length, before anything is written
+    uint64_t h[2] = {0, 0};
+    HIPTRY(hipMemcpyAsync(h, err, 16, hipMemcpyDeviceToHost, c->stream));
+    HIPTRY(hipStreamSynchronize(c->stream));
+    TRY(mark(c, 1));
+    if (uint32_t(h[0])) {
+        TRY(mark(c, 2));
+        return NKV_ERR_INVALID;
+    }
+    *out_len = h[1];
+    if (query) return mark(c, 2);
+    // d_out's 16-byte grid over out_len bytes; no Value byte, no copy
+    const uint64_t head = uint64_t(reinterpret_cast<uintptr_t>(d_out)) & 15;
+    const uint64_t tiles = h[1] ? (head + h[1] + kCopyTile - 1) / kCopyTile : 0;
+    if (out_cap < h[1] || tiles > 0x7fffffffull) {
+        TRY(mark(c, 2));
+        return NKV_ERR_INVALID;
+    }
+    HIPTRY(hipMemcpyAsync(d_out_off, off, 8 * (q + 1), hipMemcpyDeviceToDevice, c->stream));
+    if (tiles) {
+        hipLaunchKernelGGL(k_value_copy, dim3(unsigned(tiles)), dim3(kBlock), 0, c->stream,
+                           static_cast<uint8_t*>(d_out), off, src, q, h[1]);
+        HIPTRY(hipGetLastError());
+    }
+    return mark(c, 2);
+} NKV_CATCH
+
+}  // extern "C"

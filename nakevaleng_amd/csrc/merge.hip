@@ -24,6 +24,7 @@
 
 #include <vector>
 
+#include "bytes_dev.hpp"  // ld_le64, cmp_bytes, ld16_any
 #include "context.hpp"
 
 using namespace nkv;
@@ -44,27 +45,10 @@ struct Runs {  // kernel argument: the k input runs
     int k;
 };
 
-__device__ __forceinline__ uint64_t ld_le64(const uint8_t* p) {  // any alignment
-    uint64_t v = 0;
-#pragma unroll
-    for (int b = 0; b < 8; ++b) v |= uint64_t(p[b]) << (8 * b);
-    return v;
-}
-
 __device__ __forceinline__ int run_of(const Runs& R, uint32_t g) {
     int r = 0;
     while (r + 1 < R.k && g >= R.base[r + 1]) ++r;
     return r;
-}
-
-// bytes.Compare: unsigned lexicographic, a proper prefix sorts first
-__device__ inline int cmp_bytes(const uint8_t* a, uint64_t la, const uint8_t* b, uint64_t lb) {
-    const uint64_t m = la < lb ? la : lb;
-    for (uint64_t i = 0; i < m; ++i) {
-        const uint8_t x = a[i], y = b[i];
-        if (x != y) return x < y ? -1 : 1;
-    }
-    return la < lb ? -1 : (la > lb ? 1 : 0);
 }
 
 // Dense arrays over all input records (index = base[run] + index in the run).
@@ -195,10 +179,6 @@ __global__ __launch_bounds__(kBlock) void k_merge_scatter(Runs R, uint32_t N, co
     }
 }
 
-__device__ __forceinline__ uint32_t sel4(uint32_t q, uint32_t a, uint32_t b, uint32_t c, uint32_t d) {
-    return q == 0 ? a : (q == 1 ? b : (q == 2 ? c : d));
-}
-
 // Output byte o of the merged table is byte o - off[j] of the record at
 // src[j], for the j with off[j] <= o < off[j + 1].  Chunks lie on the 16-byte
 // grid of d_out's address, so every full chunk is one aligned 16-byte store; a
@@ -253,20 +233,7 @@ __global__ __launch_bounds__(kBlock) void k_merge_copy(uint8_t* __restrict__ out
         const bool whole = p >= head && p + kCopyChunk <= pend;
         if (whole && ob + kCopyChunk <= l_off[e + 1]) {
             const uint64_t S = l_src[e] + (ob - l_off[e]);
-            const uint32_t sh = uint32_t(S & 15);
-            const uint4* q = reinterpret_cast<const uint4*>(uintptr_t(S - sh));
-            uint4 v = q[0];
-            if (sh) {
-                const uint4 w = q[1];
-                const uint32_t d = sh >> 2, bs = sh & 3;
-                const uint32_t x0 = sel4(d, v.x, v.y, v.z, v.w), x1 = sel4(d, v.y, v.z, v.w, w.x),
-                               x2 = sel4(d, v.z, v.w, w.x, w.y), x3 = sel4(d, v.w, w.x, w.y, w.z),
-                               x4 = sel4(d, w.x, w.y, w.z, w.w);
-                v.x = __builtin_amdgcn_alignbyte(x1, x0, bs);
-                v.y = __builtin_amdgcn_alignbyte(x2, x1, bs);
-                v.z = __builtin_amdgcn_alignbyte(x3, x2, bs);
-                v.w = __builtin_amdgcn_alignbyte(x4, x3, bs);
-            }
+            const uint4 v = ld16_any(S);
             *reinterpret_cast<uint4*>(out + ob) = v;
         } else {
             uint32_t w[4] = {0, 0, 0, 0};

@@ -11,6 +11,10 @@ rank holds every table's root.
 The k-way merge itself (lsmtree.go:137-231) runs on the device too: merge() is
 its host-memory form, compact() uploads the runs once and chains the checksum
 check, the merge, the output table's tree and its filter with no re-upload.
+
+The read side: upload_table() keeps a Data table (and its filter) resident, and
+get_many() answers a batch of keys over resident tables in search order
+(nkv_lookup_dev, nkv_lookup_values_dev), the disk part of the engine's get.
 """
 from __future__ import annotations
 
@@ -154,7 +158,7 @@ def merge(tables: Sequence[Table], device=None) -> Table:
 
 
 def compact(tables: Sequence[Table], device=None, seed: Optional[int] = None,
-            false_positive_rate: float = 0.01, summary_page_size: Optional[int] = None) -> dict:
+            false_positive_rate: float = 0.01, summary_page_size: Optional[int] = None, resident: bool = False):
     """One compaction on the device, the runs uploaded once: every input
     record's Crc checked (nkv_tree_verify_records_dev; a bad one raises
     record.verify's "Bad Record checksum" ValueError before any merge is
@@ -167,8 +171,11 @@ def compact(tables: Sequence[Table], device=None, seed: Optional[int] = None,
     bytes, "filter": BloomFilter or None, "sources": (run << 32) | index of
     every output record}.  With `summary_page_size` the dict also holds "index"
     and "summary": the merged table's Index and Summary files
-    (nkv_index_summary_dev over the merged table where it lies).  A merge of no
-    records raises MerkleTreeError, as New does on zero leaves."""
+    (nkv_index_summary_dev over the merged table where it lies).  With
+    `resident` the return is (that dict, a ResidentTable over the merged table
+    and its filter where they lie on the device), ready for get_many with no
+    re-upload.  A merge of no records raises MerkleTreeError, as New does on
+    zero leaves."""
     import ctypes
     import torch
     from . import _lib, bloomfilter, sstable
@@ -256,4 +263,122 @@ def compact(tables: Sequence[Table], device=None, seed: Optional[int] = None,
     if d_index is not None:
         out["index"] = d_index.cpu().numpy().tobytes()
         out["summary"] = d_summary.cpu().numpy().tobytes()
+    if resident:
+        return out, ResidentTable(dev_index, d_out, nbytes, d_out_off, n, d_bits, bf.M if bf else 0,
+                                  bf.K if bf else 0, bf._seed0 if bf else 0)
     return out
+
+
+# ---------------------------------------------------------------------------
+# point lookup over resident tables (nkv_lookup_dev / nkv_lookup_values_dev)
+
+class ResidentTable:
+    """One Data table kept on a device for get_many: the stream, its record
+    offsets and, optionally, its filter words.  The handle keeps the torch
+    tensors alive; drop it to free them."""
+
+    def __init__(self, device: int, stream, nbytes: int, rec_off, n: int, bits=None, m: int = 0, k: int = 0,
+                 seed0: int = 0):
+        self.device, self.stream, self.nbytes, self.rec_off, self.n = device, stream, int(nbytes), rec_off, int(n)
+        self.bits, self.m, self.k, self.seed0 = bits, int(m), int(k), int(seed0)
+
+    def as_struct(self):
+        from . import _lib
+        return _lib.NkvLookupTable(self.stream.data_ptr(), self.nbytes, self.rec_off.data_ptr(), self.n,
+                                   self.bits.data_ptr() if self.bits is not None else None, self.m, self.k,
+                                   self.seed0)
+
+
+def upload_table(table: Table, filter=None, device=None) -> ResidentTable:
+    """Put one Data table (stream, RecSize array) on the device, with its record
+    offsets (nkv_record_offsets_dev) and, when `filter` (a BloomFilter) is
+    given, the filter's words with its M, K and first seed.  A table of no
+    records raises ValueError: the reference cannot write one."""
+    import torch
+    from . import _lib
+    data, rec_sizes = table
+    sizes = np.ascontiguousarray(rec_sizes, dtype=np.uint64)
+    n, nbytes = int(sizes.size), len(data)
+    if n == 0:
+        raise ValueError("upload_table: a table holds at least one record")
+    dev_index = rank_device(device)
+    ctx = _lib.default_context(dev_index)
+    dev = torch.device("cuda", dev_index)
+
+    def up(a):
+        return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).copy()).to(dev)
+
+    d_data, d_size = up(np.frombuffer(bytes(data) or b"\0", np.uint8)), up(sizes)
+    d_off = torch.zeros(8 * n, dtype=torch.uint8, device=dev)
+    stream = torch.cuda.current_stream(dev)
+    with ctx.on_stream(stream.cuda_stream):
+        _lib.check(_lib.lib().nkv_record_offsets_dev(ctx.h, d_size.data_ptr(), n, d_off.data_ptr()))
+        stream.synchronize()
+    d_bits, m, k, seed0 = None, 0, 0, 0
+    if filter is not None:
+        m, k, seed0 = filter.M, filter.K, filter._seed0
+        words = np.zeros(((m + 31) // 32) * 4, np.uint8)
+        contents = np.frombuffer(filter.Contents, np.uint8)
+        words[:contents.size] = contents
+        d_bits = up(words)
+    return ResidentTable(dev_index, d_data, nbytes, d_off, n, d_bits, m, k, seed0)
+
+
+def get_many(tables: Sequence[ResidentTable], keys: Sequence[bytes], device=None, stages: bool = False):
+    """The disk part of the engine's get (coreeng.go:99-160) for a batch of
+    keys over resident tables listed in search order (levels ascending, runs
+    descending): per key the Value bytes of the first table that holds it, or
+    None where no table does or that table holds a tombstone.  With `stages`
+    the return is (values, the q x T array of NKV_STAGE codes, the q hits
+    (table << 32) | record index, NKV_HIT_NONE where absent)."""
+    import ctypes
+    import torch
+    from . import _lib
+    T, q = len(tables), len(keys)
+    if not 1 <= T <= _lib.NKV_LOOKUP_MAX_TABLES:
+        raise ValueError(f"get_many takes 1..{_lib.NKV_LOOKUP_MAX_TABLES} tables, got {T}")
+    dev_index = rank_device(device if device is not None else tables[0].device)
+    if any(t.device != dev_index for t in tables):
+        raise ValueError(f"get_many: every table must be resident on device {dev_index}")
+    if q == 0:
+        return ([], np.zeros((0, T), np.uint8), np.zeros(0, np.uint64)) if stages else []
+    ctx = _lib.default_context(dev_index)
+    L = _lib.lib()
+    dev = torch.device("cuda", dev_index)
+
+    def up(a):
+        return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).copy()).to(dev)
+
+    def u8(nbytes):
+        return torch.zeros(max(int(nbytes), 16), dtype=torch.uint8, device=dev)
+
+    keys = [bytes(k) for k in keys]
+    klen = np.fromiter((len(k) for k in keys), dtype=np.uint64, count=q)
+    koff = np.zeros(q, np.uint64)
+    koff[1:] = np.cumsum(klen[:-1])
+    d_keys, d_koff, d_klen = up(np.frombuffer(b"".join(keys) or b"\0", np.uint8)), up(koff), up(klen)
+    d_hit, d_status, d_stage, d_err, d_out_off = u8(8 * q), u8(q), u8(q * T), u8(4), u8(8 * (q + 1))
+    tabs = (_lib.NkvLookupTable * T)(*[t.as_struct() for t in tables])
+    out_len = ctypes.c_uint64(0)
+    stream = torch.cuda.current_stream(dev)
+    with ctx.on_stream(stream.cuda_stream):
+        _lib.check(L.nkv_lookup_dev(ctx.h, tabs, T, d_keys.data_ptr(), d_koff.data_ptr(), d_klen.data_ptr(), q,
+                                    d_hit.data_ptr(), d_status.data_ptr(), d_stage.data_ptr(), d_err.data_ptr()),
+                   "point lookup")
+        _lib.check(L.nkv_lookup_values_dev(ctx.h, tabs, T, d_hit.data_ptr(), d_status.data_ptr(), q, None, 0, None,
+                                           ctypes.byref(out_len)), "point lookup, Value sizes")
+        if int(d_err.cpu().numpy().view(np.uint32)[0]):
+            raise _lib.NkvError(_lib.NKV_ERR_INVALID, "point lookup: a record reaches outside its table")
+        d_out = u8(out_len.value)
+        _lib.check(L.nkv_lookup_values_dev(ctx.h, tabs, T, d_hit.data_ptr(), d_status.data_ptr(), q,
+                                           d_out.data_ptr(), out_len.value, d_out_off.data_ptr(),
+                                           ctypes.byref(out_len)), "point lookup, Values")
+        stream.synchronize()
+    status = d_status.cpu().numpy()[:q]
+    off = d_out_off.cpu().numpy().view(np.uint64)[:q + 1].tolist()
+    packed = d_out.cpu().numpy()[:out_len.value].tobytes()
+    values = [packed[off[i]:off[i + 1]] if status[i] == _lib.NKV_GET_LIVE else None for i in range(q)]
+    if not stages:
+        return values
+    return (values, d_stage.cpu().numpy()[:q * T].reshape(q, T).copy(),
+            d_hit.cpu().numpy().view(np.uint64)[:q].copy())
