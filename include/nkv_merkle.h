@@ -37,6 +37,8 @@
  *   CoreEngine.get, disk    engine/coreeng/coreeng.go:99-160    nkv_lookup_dev /
  *     path (Filter.Query, FindSummaryTableEntry,                  nkv_lookup_values_dev
  *     FindIndexTableEntry, record.Deserialize per table)
+ *   Memtable.Flush over     core/memtable/memtable.go:93-116    nkv_sort_records_dev /
+ *     skiplist.Write        core/skiplist/skiplist.go:62-120    nkv_sort_records
  *
  * Conventions
  *   - Every function returns an nkv_status (0 = NKV_OK) unless noted; nothing
@@ -60,7 +62,7 @@
  *     output, not a byte before or past it (callers pack nodes, images and
  *     offset arrays next to each other in one allocation).
  *       byte strings, at any address: d_img, nkv_bloom_query_dev's d_out, the
- *         buffer of nkv_fill_splitmix64_dev, the merge's d_out, d_index and
+ *         buffer of nkv_fill_splitmix64_dev, the merge's and the sort's d_out, d_index and
  *         d_summary of nkv_index_summary_dev, d_status and d_stage of
  *         nkv_lookup_dev, d_out of nkv_lookup_values_dev;
  *       digest arrays (d_nodes, nkv_table.nodes, d_roots and d_out entries of
@@ -71,12 +73,12 @@
  *         d_out_src, d_hit), 8-byte aligned.
  *     nkv_leaf_hash*_dev write level 0 only (20 n bytes); nkv_tree_reduce_dev
  *     leaves level 0 as given; d_bits is ((m + 31) / 32) * 4 bytes; the merge
- *     writes out_len bytes and n_out entries; nkv_index_summary_dev writes
+ *     and the sort write out_len bytes and n_out entries; nkv_index_summary_dev writes
  *     *index_len and *summary_len bytes; nkv_lookup_dev writes q entries of
  *     d_hit and d_status and q T bytes of d_stage; nkv_lookup_values_dev
  *     writes *out_len bytes and q + 1 entries of d_out_off.  Inputs are never
  *     written: values, record streams, offset and length arrays, the merge's
- *     runs, and the lookup's tables, filters and query keys are read in place
+ *     runs, the sort's log, and the lookup's tables, filters and query keys are read in place
  *     (at any alignment where they are bytes).
  *   - Offsets, strides and stream lengths are full 64-bit quantities: the
  *     values, spans or records of one call may lie any distance apart inside
@@ -490,6 +492,51 @@ int nkv_merge_records_dev(nkv_ctx *ctx, const nkv_run *runs, int k, void *d_out,
 int nkv_merge_records(nkv_ctx *ctx, const uint8_t *const *streams, const uint64_t *stream_len,
                       const uint64_t *const *rec_size, const uint64_t *n, int k, uint8_t *out,
                       uint64_t out_cap, uint64_t *out_rec_size, uint64_t *n_out, uint64_t *out_len);
+
+/* ---- memtable flush (core/memtable/memtable.go:93-116) ----
+ * A write log in, the Data table the memtable would flush out.  The log holds n
+ * whole serialized records (record.go:191-199) in arrival order, one behind the
+ * other: what CoreEngine.put hands to Memtable.Add, or a WAL segment's records.
+ * No key order is required.  skiplist.Write (skiplist.go:62-120) compares keys
+ * with bytes.Compare and replaces the whole record of a key that is already
+ * there, so the flushed table holds one record per distinct key in ascending
+ * key order (unsigned lexicographic; a proper prefix sorts first, the empty key
+ * is smallest), and the record kept for a key is the one that arrived last,
+ * copied byte for byte: Timestamp, Status and TypeInfo come along, a later
+ * tombstone shadows a live record, and a later write with an older Timestamp
+ * still wins (unlike the merge's rule).  In closed form: sort by (key
+ * ascending, arrival index ascending) and keep position s iff it is the last
+ * or the key at s + 1 differs.  That order is total, so there is no tie rule.
+ * Memtable.Remove (the tombstone bit set in place) has no serialized form and
+ * is not covered; the engine deletes through put.
+ *
+ * Errors: NKV_ERR_INVALID for a null context or a null pointer with n > 0,
+ * n > 2^31 - 1, out_cap < log_len, log_len / 30 < n (n = 0 takes log_len = 0),
+ * d_rec_off[0] != 0, a header outside the log, a KeySize or ValueSize that
+ * reaches outside the log, and a record that does not end where the next one
+ * starts (the last at log_len).  The log is validated by a kernel of its own
+ * before any kernel follows an offset or copies a record; when it refuses,
+ * nothing further is launched and the context stays usable.  n = 0 returns
+ * NKV_OK with *n_out = 0.  Record checksums are not checked here
+ * (nkv_record_crc_dev / nkv_tree_verify_records_dev in front do that). */
+/* Device-resident form.  d_log (log_len bytes, any alignment) with d_rec_off (n
+ * offsets, as nkv_record_offsets_dev writes them).  d_out (out_cap >= log_len
+ * bytes, any alignment) receives the flushed stream, d_out_off (n entries) the
+ * offset of each output record, d_out_src (nullable, n entries) the arrival
+ * index of the input record each output record was copied from.  *n_out /
+ * *out_len (host): records and bytes written; the call synchronizes.  d_out /
+ * d_out_off feed nkv_tree_from_records_dev, nkv_bloom_insert_records_dev,
+ * nkv_index_summary_dev, nkv_record_crc_dev and nkv_lookup_dev as they are.
+ * Under NKV_TIMING_EVENTS the "leaf" interval is sort + survive + scans +
+ * scatter and the "reduce" interval the copy kernel. */
+int nkv_sort_records_dev(nkv_ctx *ctx, const void *d_log, uint64_t log_len, const uint64_t *d_rec_off, uint64_t n,
+                         void *d_out, uint64_t out_cap, uint64_t *d_out_off, uint64_t *d_out_src,
+                         uint64_t *n_out, uint64_t *out_len);
+/* Host-memory form: log (log_len bytes) with the RecSize of each of its n
+ * records in rec_size (they must add up to log_len); out (out_cap >= log_len)
+ * and out_rec_size (n entries) receive the flushed table. */
+int nkv_sort_records(nkv_ctx *ctx, const uint8_t *log, uint64_t log_len, const uint64_t *rec_size, uint64_t n,
+                     uint8_t *out, uint64_t out_cap, uint64_t *out_rec_size, uint64_t *n_out, uint64_t *out_len);
 
 /* ---- Index and Summary tables (core/sstable/sstable.go:76-139) ----
  * makeIndexAndSummary over a Data table: for records i = 0..n-1 with key K_i

@@ -162,6 +162,8 @@ SIGNATURES = {
     "nkv_merge_records_dev": (_int, [_vp, ctypes.POINTER(NkvRun), _int, _vp, _u64, _vp, _vp, _u64p, _u64p]),
     "nkv_merge_records": (_int, [_vp, ctypes.POINTER(_vp), _u64p, ctypes.POINTER(_vp), _u64p, _int, _vp, _u64, _vp,
                                  _u64p, _u64p]),
+    "nkv_sort_records_dev": (_int, [_vp, _vp, _u64, _vp, _u64, _vp, _u64, _vp, _vp, _u64p, _u64p]),
+    "nkv_sort_records": (_int, [_vp, _vp, _u64, _vp, _u64, _vp, _u64, _vp, _u64p, _u64p]),
     "nkv_summary_entries": (_u64, [_u64, _u64]),
     "nkv_index_summary_dev": (_int, [_vp, _vp, _u64, _vp, _u64, _u64, _vp, _u64, _vp, _u64, _u64p, _u64p]),
     "nkv_index_summary_from_records": (_int, [_vp, _vp, _u64, _vp, _u64, _u64, _vp, _u64, _vp, _u64, _u64p,

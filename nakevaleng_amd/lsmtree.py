@@ -12,6 +12,11 @@ The k-way merge itself (lsmtree.go:137-231) runs on the device too: merge() is
 its host-memory form, compact() uploads the runs once and chains the checksum
 check, the merge, the output table's tree and its filter with no re-upload.
 
+The step in front of compaction runs there as well: sort_log() is the memtable
+flush of a write log in arrival order in its host-memory form, and flush_log()
+uploads the log once and chains the checksum check, the sort
+(nkv_sort_records_dev) and the flushed table's tree, filter, Index and Summary.
+
 The read side: upload_table() keeps a Data table (and its filter) resident, and
 get_many() answers a batch of keys over resident tables in search order
 (nkv_lookup_dev, nkv_lookup_values_dev), the disk part of the engine's get.
@@ -178,8 +183,7 @@ def compact(tables: Sequence[Table], device=None, seed: Optional[int] = None,
     zero leaves."""
     import ctypes
     import torch
-    from . import _lib, bloomfilter, sstable
-    from .merkletree import MerkleTreeError
+    from . import _lib
     _check_runs(tables)
     k = len(tables)
     dev_index = rank_device(device)
@@ -227,28 +231,48 @@ def compact(tables: Sequence[Table], device=None, seed: Optional[int] = None,
         _lib.check(L.nkv_merge_records_dev(ctx.h, runs, k, d_out.data_ptr(), total, d_out_off.data_ptr(),
                                            d_out_src.data_ptr(), ctypes.byref(n_out), ctypes.byref(out_len)),
                    "compaction merge")
-        n, nbytes = n_out.value, out_len.value
-        if n == 0:
-            raise MerkleTreeError("cannot build Merkle Tree from 0 nodes")
-        d_nodes, d_img = u8(L.nkv_total_nodes(n) * 20), u8(L.nkv_bfs_size(n))
-        d_err = u8(4)
-        _lib.check(L.nkv_tree_from_records_dev(ctx.h, d_out.data_ptr(), nbytes, d_out_off.data_ptr(), n,
-                                               d_nodes.data_ptr(), d_err.data_ptr()), "compaction Merkle step")
-        _lib.check(L.nkv_bfs_image_dev(ctx.h, d_nodes.data_ptr(), n, d_img.data_ptr()), "Serialize image")
-        bf = d_bits = None
-        if seed is not None:
-            bf = bloomfilter.New(n, false_positive_rate, seed=seed, ctx=ctx)
-            d_bits = u8(((bf.M + 31) // 32) * 4)
-            _lib.check(L.nkv_bloom_insert_records_dev(ctx.h, d_out.data_ptr(), nbytes, d_out_off.data_ptr(), n,
-                                                      bf.M, bf.K, bf.HashSeeds[0] if bf.K else 0,
-                                                      d_bits.data_ptr()), "compaction filter")
-        d_index = d_summary = None
-        if summary_page_size is not None:
-            d_index, d_summary = sstable.index_summary_dev(ctx, dev, d_out.data_ptr(), nbytes, d_out_off.data_ptr(),
-                                                           n, summary_page_size)
-        stream.synchronize()
+        return _table_secondaries(ctx, dev_index, stream, d_out, d_out_off, d_out_src, n_out.value, out_len.value,
+                                  "compaction", seed, false_positive_rate, summary_page_size, resident)
+
+
+def _table_secondaries(ctx, dev_index, stream, d_out, d_out_off, d_out_src, n, nbytes, what, seed,
+                       false_positive_rate, summary_page_size, resident):
+    """What compact and flush_log do with the Data table their first step left
+    on the device (d_out, d_out_off, d_out_src: n records, nbytes bytes), on
+    `stream` with the context already on it: the tree and its Serialize image,
+    the filter when `seed` is given, the Index and Summary when
+    `summary_page_size` is, then the downloads into the result dict (and the
+    ResidentTable when `resident`)."""
+    import torch
+    from . import _lib, bloomfilter, sstable
+    from .merkletree import MerkleTreeError
+    L = _lib.lib()
+    dev = torch.device("cuda", dev_index)
+
+    def u8(nbytes):
+        return torch.zeros(max(int(nbytes), 16), dtype=torch.uint8, device=dev)
+
+    if n == 0:
+        raise MerkleTreeError("cannot build Merkle Tree from 0 nodes")
+    d_nodes, d_img = u8(L.nkv_total_nodes(n) * 20), u8(L.nkv_bfs_size(n))
+    d_err = u8(4)
+    _lib.check(L.nkv_tree_from_records_dev(ctx.h, d_out.data_ptr(), nbytes, d_out_off.data_ptr(), n,
+                                           d_nodes.data_ptr(), d_err.data_ptr()), f"{what} Merkle step")
+    _lib.check(L.nkv_bfs_image_dev(ctx.h, d_nodes.data_ptr(), n, d_img.data_ptr()), "Serialize image")
+    bf = d_bits = None
+    if seed is not None:
+        bf = bloomfilter.New(n, false_positive_rate, seed=seed, ctx=ctx)
+        d_bits = u8(((bf.M + 31) // 32) * 4)
+        _lib.check(L.nkv_bloom_insert_records_dev(ctx.h, d_out.data_ptr(), nbytes, d_out_off.data_ptr(), n,
+                                                  bf.M, bf.K, bf.HashSeeds[0] if bf.K else 0,
+                                                  d_bits.data_ptr()), f"{what} filter")
+    d_index = d_summary = None
+    if summary_page_size is not None:
+        d_index, d_summary = sstable.index_summary_dev(ctx, dev, d_out.data_ptr(), nbytes, d_out_off.data_ptr(),
+                                                       n, summary_page_size)
+    stream.synchronize()
     if int(d_err.cpu().numpy().view(np.uint32)[0]):
-        raise _lib.NkvError(_lib.NKV_ERR_INVALID, "compaction Merkle step")
+        raise _lib.NkvError(_lib.NKV_ERR_INVALID, f"{what} Merkle step")
     off = d_out_off.cpu().numpy().view(np.uint64)[:n]
     sizes = np.diff(np.append(off, np.uint64(nbytes))).astype(np.uint64)
     nodes = d_nodes.cpu().numpy()
@@ -267,6 +291,96 @@ def compact(tables: Sequence[Table], device=None, seed: Optional[int] = None,
         return out, ResidentTable(dev_index, d_out, nbytes, d_out_off, n, d_bits, bf.M if bf else 0,
                                   bf.K if bf else 0, bf._seed0 if bf else 0)
     return out
+
+
+# ---------------------------------------------------------------------------
+# the memtable flush (nkv_sort_records / nkv_sort_records_dev)
+
+def sort_log(log: Table, device=None) -> Table:
+    """Memtable.Flush's Data table (memtable.go:93-116 over skiplist.go:62-120)
+    of a write log held in host memory: `log` is (stream, RecSize array) with
+    the records in arrival order, any key order.  One record per distinct key
+    in ascending key order, the last arrival of each key kept whatever its
+    Timestamp or Status, every record copied byte for byte.  Returns the
+    flushed (stream, RecSize array)."""
+    import ctypes
+    from . import _lib
+    data, rec_sizes = log
+    ctx = _lib.default_context(rank_device(device))
+    buf = np.frombuffer(bytes(data) + b"\0", dtype=np.uint8)
+    sizes = np.ascontiguousarray(rec_sizes, dtype=np.uint64)
+    n = int(sizes.size)
+    sizes_p = sizes if n else np.zeros(1, np.uint64)
+    out = np.zeros(buf.size, np.uint8)
+    out_sizes = np.zeros(n + 1, np.uint64)
+    n_out, out_len = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    _lib.check(_lib.lib().nkv_sort_records(ctx.h, buf.ctypes.data, buf.size - 1, sizes_p.ctypes.data, n,
+                                           out.ctypes.data, out.size - 1, out_sizes.ctypes.data,
+                                           ctypes.byref(n_out), ctypes.byref(out_len)), "memtable flush")
+    return out[:out_len.value].tobytes(), out_sizes[:n_out.value].copy()
+
+
+def flush_log(log: Table, device=None, seed: Optional[int] = None, false_positive_rate: float = 0.01,
+              summary_page_size: Optional[int] = None, resident: bool = False):
+    """Memtable.Flush's MakeTable on the device from one upload of a write log
+    (stream, RecSize array) in arrival order: every record's Crc checked
+    (nkv_tree_verify_records_dev; a bad one raises record.verify's "Bad Record
+    checksum" ValueError before any sort is launched, where WAL replay's
+    Deserialize panics), the flush itself (nkv_sort_records_dev), then what
+    compact does with its merged table: the tree and Serialize image, the
+    filter when `seed` is given, the Index and Summary when
+    `summary_page_size` is.
+
+    Returns compact's dict: "table", "root", "image", "filter", "sources" (the
+    arrival index of every output record) and, with `summary_page_size`,
+    "index" and "summary"; with `resident` (that dict, a ResidentTable over the
+    flushed table and its filter where they lie on the device).  An empty log
+    raises MerkleTreeError, as New does on zero leaves."""
+    import ctypes
+    import torch
+    from . import _lib
+    from .merkletree import MerkleTreeError
+    data, rec_sizes = log
+    sizes = np.ascontiguousarray(rec_sizes, dtype=np.uint64)
+    n, nbytes = int(sizes.size), len(data)
+    if n == 0:
+        if nbytes:
+            raise _lib.NkvError(_lib.NKV_ERR_INVALID, "memtable flush: bytes and no records")
+        raise MerkleTreeError("cannot build Merkle Tree from 0 nodes")
+    dev_index = rank_device(device)
+    ctx = _lib.default_context(dev_index)
+    L = _lib.lib()
+    dev = torch.device("cuda", dev_index)
+
+    def up(a):
+        return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).copy()).to(dev)
+
+    def u8(nbytes):
+        return torch.zeros(max(int(nbytes), 16), dtype=torch.uint8, device=dev)
+
+    stream = torch.cuda.current_stream(dev)
+    with ctx.on_stream(stream.cuda_stream):
+        d_data = up(np.frombuffer(bytes(data), np.uint8))
+        d_size, d_off = up(sizes), u8(8 * n)
+        _lib.check(L.nkv_record_offsets_dev(ctx.h, d_size.data_ptr(), n, d_off.data_ptr()))
+        d_nodes, d_crc, d_stats = u8(L.nkv_total_nodes(n) * 20), u8(4 * n), u8(24)
+        _lib.check(L.nkv_tree_verify_records_dev(ctx.h, d_data.data_ptr(), nbytes, d_off.data_ptr(), n,
+                                                 d_nodes.data_ptr(), d_crc.data_ptr(), d_stats.data_ptr()),
+                   "flush read")
+        bad, first, hdr = d_stats.cpu().numpy().view(np.uint64).tolist()
+        if hdr:
+            raise _lib.NkvError(_lib.NKV_ERR_INVALID, "flush read")
+        if bad:
+            got = int(d_crc.cpu().numpy().view(np.uint32)[first])
+            stored = int(np.frombuffer(bytes(data), "<u4", 1, int(sizes[:first].sum()))[0])
+            raise ValueError(f"Bad Record checksum (got {got}, expected {stored})")
+        d_out, d_out_off, d_out_src = u8(nbytes), u8(8 * n), u8(8 * n)
+        n_out, out_len = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        _lib.check(L.nkv_sort_records_dev(ctx.h, d_data.data_ptr(), nbytes, d_off.data_ptr(), n, d_out.data_ptr(),
+                                          nbytes, d_out_off.data_ptr(), d_out_src.data_ptr(), ctypes.byref(n_out),
+                                          ctypes.byref(out_len)), "memtable flush")
+        return _table_secondaries(ctx, dev_index, stream, d_out, d_out_off, d_out_src, n_out.value, out_len.value,
+                                  "flush", seed, false_positive_rate, summary_page_size, resident)
 
 
 # ---------------------------------------------------------------------------
