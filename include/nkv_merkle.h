@@ -39,6 +39,8 @@
  *     FindIndexTableEntry, record.Deserialize per table)
  *   Memtable.Flush over     core/memtable/memtable.go:93-116    nkv_sort_records_dev /
  *     skiplist.Write        core/skiplist/skiplist.go:62-120    nkv_sort_records
+ *   record.New / ToBytes    core/record/record.go:49-60,175-187 nkv_encode_records_dev /
+ *   wal.flushPartialBufferToSegment  core/wal/wal.go:199-232    nkv_encode_records
  *
  * Conventions
  *   - Every function returns an nkv_status (0 = NKV_OK) unless noted; nothing
@@ -64,19 +66,23 @@
  *       byte strings, at any address: d_img, nkv_bloom_query_dev's d_out, the
  *         buffer of nkv_fill_splitmix64_dev, the merge's and the sort's d_out, d_index and
  *         d_summary of nkv_index_summary_dev, d_status and d_stage of
- *         nkv_lookup_dev, d_out of nkv_lookup_values_dev;
+ *         nkv_lookup_dev, d_out of nkv_lookup_values_dev, d_out of
+ *         nkv_encode_records_dev;
  *       digest arrays (d_nodes, nkv_table.nodes, d_roots and d_out entries of
  *         the group calls), 4-byte aligned: level starts inside a nodes buffer
  *         are multiples of 20 bytes, no more;
- *       uint32_t arrays and filter words (d_crc, d_err, d_bits), 4-byte aligned;
- *       uint64_t arrays (d_rec_off, d_voff, d_vlen, d_stats, d_out_off,
- *         d_out_src, d_hit), 8-byte aligned.
+ *       uint32_t arrays and filter words (d_crc, the encode's d_crc included,
+ *         d_err, d_bits), 4-byte aligned;
+ *       uint64_t arrays (d_rec_off, d_voff, d_vlen, d_stats, d_out_off, the
+ *         encode's d_out_off included, d_out_src, d_hit), 8-byte aligned.
  *     nkv_leaf_hash*_dev write level 0 only (20 n bytes); nkv_tree_reduce_dev
  *     leaves level 0 as given; d_bits is ((m + 31) / 32) * 4 bytes; the merge
  *     and the sort write out_len bytes and n_out entries; nkv_index_summary_dev writes
  *     *index_len and *summary_len bytes; nkv_lookup_dev writes q entries of
  *     d_hit and d_status and q T bytes of d_stage; nkv_lookup_values_dev
- *     writes *out_len bytes and q + 1 entries of d_out_off.  Inputs are never
+ *     writes *out_len bytes and q + 1 entries of d_out_off;
+ *     nkv_encode_records_dev writes *out_len bytes and n entries of d_out_off
+ *     and of d_crc.  Inputs are never
  *     written: values, record streams, offset and length arrays, the merge's
  *     runs, the sort's log, and the lookup's tables, filters and query keys are read in place
  *     (at any alignment where they are bytes).
@@ -537,6 +543,64 @@ int nkv_sort_records_dev(nkv_ctx *ctx, const void *d_log, uint64_t log_len, cons
  * and out_rec_size (n entries) receive the flushed table. */
 int nkv_sort_records(nkv_ctx *ctx, const uint8_t *log, uint64_t log_len, const uint64_t *rec_size, uint64_t n,
                      uint8_t *out, uint64_t out_cap, uint64_t *out_rec_size, uint64_t *n_out, uint64_t *out_len);
+
+/* ---- record encode (core/record/record.go:49-60,175-187) ----
+ * The first step of the write path: CoreEngine.put calls record.New(key, val),
+ * Record.ToBytes lays the record out, and the WAL appends those bytes
+ * (wal.flushPartialBufferToSegment, core/wal/wal.go:199-232).  Here a batch of
+ * n puts goes in and the write log comes out: record i is, little endian,
+ *   Crc u32 | Timestamp i64 | Status u8 | TypeInfo u8 | KeySize u64 |
+ *   ValueSize u64 | Key | Value
+ * with Crc = crc32.ChecksumIEEE(Key ++ Value) (record.go:51; Timestamp, Status
+ * and TypeInfo do not enter it) and TotalSize = 30 + KeySize + ValueSize, the
+ * records one behind the other in input order.  record.New stamps
+ * time.Now().Unix(), Status 0 and TypeInfo 0; NewTyped sets TypeInfo and
+ * CoreEngine.Delete re-puts with Status |= 1, so the three are inputs: one
+ * Timestamp for the batch or one per record, Status and TypeInfo 0 or one per
+ * record.  The output feeds nkv_sort_records_dev and every other records
+ * entry as it is. */
+typedef struct nkv_puts {  /* pointers on the context's device (_dev form) or in host memory (host form) */
+    const void *keys;      uint64_t keys_len;  /* key i   = keys[koff[i] .. koff[i] + klen[i]) */
+    const uint64_t *koff;  const uint64_t *klen;
+    const void *vals;      uint64_t vals_len;  /* value i = vals[voff[i] .. voff[i] + vlen[i]) */
+    const uint64_t *voff;  const uint64_t *vlen;
+    const int64_t *ts;     /* n Timestamps, or NULL: ts_all in every record */
+    int64_t ts_all;
+    const uint8_t *status; /* n Status bytes, or NULL: 0 */
+    const uint8_t *type;   /* n TypeInfo bytes, or NULL: 0 */
+    uint64_t n;
+} nkv_puts;
+/* Device form.  d_out (any byte alignment) receives the log: exactly *out_len
+ * = 30 n + sum of klen + sum of vlen bytes are written; d_out_off (8-byte
+ * aligned) the n record offsets; d_crc (nullable, 4-byte aligned) the n
+ * checksums.  Keys and values may sit at any alignment, their spans may
+ * overlap or repeat (one key or one value used by many records), and the two
+ * blobs may lie any distance apart; koff, klen, voff, vlen and ts are 8-byte
+ * aligned.  With d_out NULL the call is a size query: NKV_OK and the length
+ * (d_out_off and d_crc are ignored and may be NULL).  A kernel checks every
+ * span against its blob first and the host reads its verdict and the total
+ * once (the call's one synchronize) before any writer is launched; after
+ * NKV_OK the log is complete in stream order on the context's stream.
+ * NKV_ERR_INVALID, with nothing written and the context still usable, for: a
+ * null context, puts or out_len; n > 2^31 - 1; n > 0 with a null koff, klen,
+ * voff or vlen; keys NULL with keys_len > 0, and the same for vals; a span
+ * outside its blob (koff[i] > keys_len or klen[i] > keys_len - koff[i], the
+ * same for values: a wrapped off + len is caught); out_cap < *out_len (the
+ * length still reported, so the caller can retry); d_out_off NULL while d_out
+ * is not and n > 0; keys_len + vals_len wrapping or n (30 + keys_len +
+ * vals_len) >= 2^64 (checked before any launch); an output whose 16 KiB tiles
+ * would pass 2^31 - 1.  n = 0 returns NKV_OK with *out_len = 0 and writes
+ * nothing.  Under NKV_TIMING_EVENTS the "leaf" interval is everything before
+ * the writer, the "reduce" interval the writer, the checksums and the patch of
+ * the Crc fields. */
+int nkv_encode_records_dev(nkv_ctx *ctx, const nkv_puts *puts, void *d_out, uint64_t out_cap,
+                           uint64_t *d_out_off, uint32_t *d_crc, uint64_t *out_len);
+/* Host-memory form: the same struct with host pointers; uploads, runs the
+ * device form and downloads.  out (out_cap bytes) receives the log,
+ * out_rec_size the n TotalSizes, crc_out (nullable) the n checksums.  With out
+ * NULL it is a size query.  Synchronous. */
+int nkv_encode_records(nkv_ctx *ctx, const nkv_puts *puts, uint8_t *out, uint64_t out_cap,
+                       uint64_t *out_rec_size, uint32_t *crc_out, uint64_t *out_len);
 
 /* ---- Index and Summary tables (core/sstable/sstable.go:76-139) ----
  * makeIndexAndSummary over a Data table: for records i = 0..n-1 with key K_i

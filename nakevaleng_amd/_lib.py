@@ -85,6 +85,14 @@ class NkvLookupTable(ctypes.Structure):
                 ("m", ctypes.c_uint32), ("k", ctypes.c_uint32), ("seed0", ctypes.c_uint32)]
 
 
+class NkvPuts(ctypes.Structure):
+    """struct nkv_puts: a batch of (key, value) pairs for nkv_encode_records[_dev]
+    (ts None = ts_all in every record; status / type None = 0)."""
+    _fields_ = [("keys", _vp), ("keys_len", _u64), ("koff", _vp), ("klen", _vp), ("vals", _vp), ("vals_len", _u64),
+                ("voff", _vp), ("vlen", _vp), ("ts", _vp), ("ts_all", ctypes.c_int64), ("status", _vp), ("type", _vp),
+                ("n", _u64)]
+
+
 NKV_MERGE_MAX_RUNS = 16
 NKV_LOOKUP_MAX_TABLES = 32
 NKV_STAGE_NOT_SEARCHED = 0
@@ -164,6 +172,8 @@ SIGNATURES = {
                                  _u64p, _u64p]),
     "nkv_sort_records_dev": (_int, [_vp, _vp, _u64, _vp, _u64, _vp, _u64, _vp, _vp, _u64p, _u64p]),
     "nkv_sort_records": (_int, [_vp, _vp, _u64, _vp, _u64, _vp, _u64, _vp, _u64p, _u64p]),
+    "nkv_encode_records_dev": (_int, [_vp, ctypes.POINTER(NkvPuts), _vp, _u64, _vp, _vp, _u64p]),
+    "nkv_encode_records": (_int, [_vp, ctypes.POINTER(NkvPuts), _vp, _u64, _vp, _vp, _u64p]),
     "nkv_summary_entries": (_u64, [_u64, _u64]),
     "nkv_index_summary_dev": (_int, [_vp, _vp, _u64, _vp, _u64, _u64, _vp, _u64, _vp, _u64, _u64p, _u64p]),
     "nkv_index_summary_from_records": (_int, [_vp, _vp, _u64, _vp, _u64, _u64, _vp, _u64, _vp, _u64, _u64p,

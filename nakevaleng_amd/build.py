@@ -18,7 +18,8 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
 SO = os.path.join(PKG, "libnkvmerkle.so")
-SOURCES = ["kernels.hip", "crc.hip", "bloom.hip", "merge.hip", "memtable.hip", "index.hip", "lookup.hip", "capi.cpp",
+SOURCES = ["kernels.hip", "crc.hip", "bloom.hip", "merge.hip", "memtable.hip", "index.hip", "lookup.hip", "encode.hip",
+           "capi.cpp",
            "group.cpp", "host_stage.cpp"]
 HEADERS = ["internal.hpp", "context.hpp", "sha1_dev.hpp", "host_stage.hpp", "crc_dev.hpp", "murmur_dev.hpp",
            "bytes_dev.hpp", "merge_copy_dev.hpp"]

@@ -16,6 +16,9 @@ The step in front of compaction runs there as well: sort_log() is the memtable
 flush of a write log in arrival order in its host-memory form, and flush_log()
 uploads the log once and chains the checksum check, the sort
 (nkv_sort_records_dev) and the flushed table's tree, filter, Index and Summary.
+flush_puts() starts one step earlier, from the keys and values themselves: it
+encodes the write log on the device (nkv_encode_records_dev, record.New /
+ToBytes) and goes on as flush_log does, with no host serialization.
 
 The read side: upload_table() keeps a Data table (and its filter) resident, and
 get_many() answers a batch of keys over resident tables in search order
@@ -336,7 +339,6 @@ def flush_log(log: Table, device=None, seed: Optional[int] = None, false_positiv
     "index" and "summary"; with `resident` (that dict, a ResidentTable over the
     flushed table and its filter where they lie on the device).  An empty log
     raises MerkleTreeError, as New does on zero leaves."""
-    import ctypes
     import torch
     from . import _lib
     from .merkletree import MerkleTreeError
@@ -374,13 +376,86 @@ def flush_log(log: Table, device=None, seed: Optional[int] = None, false_positiv
             got = int(d_crc.cpu().numpy().view(np.uint32)[first])
             stored = int(np.frombuffer(bytes(data), "<u4", 1, int(sizes[:first].sum()))[0])
             raise ValueError(f"Bad Record checksum (got {got}, expected {stored})")
-        d_out, d_out_off, d_out_src = u8(nbytes), u8(8 * n), u8(8 * n)
-        n_out, out_len = ctypes.c_uint64(0), ctypes.c_uint64(0)
-        _lib.check(L.nkv_sort_records_dev(ctx.h, d_data.data_ptr(), nbytes, d_off.data_ptr(), n, d_out.data_ptr(),
-                                          nbytes, d_out_off.data_ptr(), d_out_src.data_ptr(), ctypes.byref(n_out),
-                                          ctypes.byref(out_len)), "memtable flush")
-        return _table_secondaries(ctx, dev_index, stream, d_out, d_out_off, d_out_src, n_out.value, out_len.value,
-                                  "flush", seed, false_positive_rate, summary_page_size, resident)
+        return _flush_tail(ctx, dev_index, stream, d_data, nbytes, d_off, n, seed, false_positive_rate,
+                           summary_page_size, resident)
+
+
+def _flush_tail(ctx, dev_index, stream, d_log, nbytes, d_off, n, seed, false_positive_rate, summary_page_size,
+                resident):
+    """What flush_log and flush_puts do with the write log their first step
+    left on the device (d_log of nbytes bytes, d_off its n record offsets), on
+    `stream` with the context already on it: the flush itself
+    (nkv_sort_records_dev), then _table_secondaries over the flushed table."""
+    import ctypes
+    import torch
+    from . import _lib
+    dev = torch.device("cuda", dev_index)
+
+    def u8(nbytes):
+        return torch.zeros(max(int(nbytes), 16), dtype=torch.uint8, device=dev)
+
+    d_out, d_out_off, d_out_src = u8(nbytes), u8(8 * n), u8(8 * n)
+    n_out, out_len = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    _lib.check(_lib.lib().nkv_sort_records_dev(ctx.h, d_log.data_ptr(), nbytes, d_off.data_ptr(), n,
+                                               d_out.data_ptr(), nbytes, d_out_off.data_ptr(), d_out_src.data_ptr(),
+                                               ctypes.byref(n_out), ctypes.byref(out_len)), "memtable flush")
+    return _table_secondaries(ctx, dev_index, stream, d_out, d_out_off, d_out_src, n_out.value, out_len.value,
+                              "flush", seed, false_positive_rate, summary_page_size, resident)
+
+
+def flush_puts(keys, values, timestamps=None, status=None, type_info=None, device=None, seed: Optional[int] = None,
+               false_positive_rate: float = 0.01, summary_page_size: Optional[int] = None, resident: bool = False):
+    """The reference's whole write path on the device from one upload of a batch
+    of puts: record.New / ToBytes for every (key, value) (nkv_encode_records_dev;
+    timestamps, status and type_info as record.encode_many takes them), then
+    what flush_log does behind its upload: the flush (nkv_sort_records_dev) and
+    the flushed table's tree, filter, Index and Summary.  No checksum pass is
+    made: the checksums were just computed.
+
+    Returns flush_log's dict (with `resident`: that dict and the ResidentTable)
+    plus "log": the encoded (stream, RecSize array) in arrival order, the bytes
+    the WAL would append.  Zero puts raise MerkleTreeError, as flush_log does."""
+    import ctypes
+    import torch
+    from . import _lib, record
+    from .merkletree import MerkleTreeError
+    p = record.pack_puts(keys, values, timestamps, status, type_info)
+    n = p["n"]
+    if n == 0:
+        raise MerkleTreeError("cannot build Merkle Tree from 0 nodes")
+    dev_index = rank_device(device)
+    ctx = _lib.default_context(dev_index)
+    L = _lib.lib()
+    dev = torch.device("cuda", dev_index)
+
+    def up(a):
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a).view(np.uint8)
+        return torch.from_numpy(a.copy() if a.size else np.zeros(16, np.uint8)).to(dev)
+
+    def ptr(t):
+        return None if t is None else t.data_ptr()
+
+    stream = torch.cuda.current_stream(dev)
+    with ctx.on_stream(stream.cuda_stream):
+        d = {k: up(p[k]) for k in ("keys", "koff", "klen", "vals", "voff", "vlen", "ts", "status", "type")}
+        puts = _lib.NkvPuts(ptr(d["keys"]), p["keys"].size, ptr(d["koff"]), ptr(d["klen"]), ptr(d["vals"]),
+                            p["vals"].size, ptr(d["voff"]), ptr(d["vlen"]), ptr(d["ts"]), p["ts_all"],
+                            ptr(d["status"]), ptr(d["type"]), n)
+        nbytes = 30 * n + int(p["klen"].sum()) + int(p["vlen"].sum())
+        d_log = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
+        d_off = torch.zeros(8 * n, dtype=torch.uint8, device=dev)
+        out_len = ctypes.c_uint64(0)
+        _lib.check(L.nkv_encode_records_dev(ctx.h, ctypes.byref(puts), d_log.data_ptr(), nbytes, d_off.data_ptr(),
+                                            None, ctypes.byref(out_len)), "record encode")
+        assert out_len.value == nbytes
+        got = _flush_tail(ctx, dev_index, stream, d_log, nbytes, d_off, n, seed, false_positive_rate,
+                          summary_page_size, resident)
+        off = d_off.cpu().numpy().view(np.uint64)
+        sizes = np.diff(np.append(off, np.uint64(nbytes))).astype(np.uint64)
+        (got[0] if resident else got)["log"] = (d_log.cpu().numpy().tobytes(), sizes)
+        return got
 
 
 # ---------------------------------------------------------------------------

@@ -77,6 +77,73 @@ def data_table(records: Iterable[Record]) -> Tuple[bytes, np.ndarray]:
     return b"".join(parts), np.asarray(sizes, dtype=np.uint64)
 
 
+def _per_record(what, x, n, dtype):
+    """None, one int for the batch, or a sequence of n: (array or None, the one value)."""
+    if x is None:
+        return None, 0
+    if np.ndim(x) == 0:
+        return None, int(x)
+    a = np.ascontiguousarray(x, dtype=dtype)
+    if a.shape != (n,):
+        raise ValueError(f"{what}: {a.size} entries for {n} records")
+    return a, 0
+
+
+def pack_puts(keys, values, timestamps=None, status=None, type_info=None):
+    """A batch of puts as nkv_puts takes it: the keys and the values packed one
+    behind the other, their offset and length arrays, and the per-record header
+    fields.  Returns a dict of numpy arrays (ts / status / type None where one
+    value serves the batch) with "ts_all" and "n".  timestamps None stamps one
+    int(time.time()) for the batch, as record.New does per record."""
+    keys, values = [bytes(k) for k in keys], [bytes(v) for v in values]
+    n = len(keys)
+    if len(values) != n:
+        raise ValueError(f"encode: {n} keys and {len(values)} values")
+    klen = np.fromiter((len(k) for k in keys), dtype=np.uint64, count=n)
+    vlen = np.fromiter((len(v) for v in values), dtype=np.uint64, count=n)
+    koff, voff = np.zeros(n, np.uint64), np.zeros(n, np.uint64)
+    if n > 1:
+        koff[1:], voff[1:] = np.cumsum(klen[:-1]), np.cumsum(vlen[:-1])
+    ts, ts_all = _per_record("timestamps", int(time.time()) if timestamps is None else timestamps, n, np.int64)
+    st, st_all = _per_record("status", status, n, np.uint8)
+    ty, ty_all = _per_record("type_info", type_info, n, np.uint8)
+    if st is None and st_all:
+        st = np.full(n, st_all, np.uint8)
+    if ty is None and ty_all:
+        ty = np.full(n, ty_all, np.uint8)
+    return {"keys": np.frombuffer(b"".join(keys), np.uint8), "koff": koff, "klen": klen,
+            "vals": np.frombuffer(b"".join(values), np.uint8), "voff": voff, "vlen": vlen,
+            "ts": ts, "ts_all": ts_all, "status": st, "type": ty, "n": n}
+
+
+def encode_many(keys, values, timestamps=None, status=None, type_info=None, ctx=None) -> Tuple[bytes, np.ndarray]:
+    """record.New(key, val).ToBytes() for a batch of puts on the device
+    (nkv_encode_records; record.go:49-60, 175-187): the write log, which is what
+    the WAL appends (wal.go:199-232), and each record's TotalSize.  timestamps:
+    None = one int(time.time()) for the batch, an int = that value in every
+    record, a sequence = one per record; status and type_info: None (0), an int
+    or a sequence.  A length mismatch raises ValueError."""
+    import ctypes
+    from nakevaleng_amd import _lib
+    ctx = ctx or _lib.default_context()
+    p = pack_puts(keys, values, timestamps, status, type_info)
+    n = p["n"]
+
+    def ptr(a):
+        return None if a is None or a.size == 0 else a.ctypes.data
+
+    puts = _lib.NkvPuts(ptr(p["keys"]), p["keys"].size, ptr(p["koff"]), ptr(p["klen"]), ptr(p["vals"]),
+                        p["vals"].size, ptr(p["voff"]), ptr(p["vlen"]), ptr(p["ts"]), p["ts_all"], ptr(p["status"]),
+                        ptr(p["type"]), n)
+    total = 30 * n + int(p["klen"].sum()) + int(p["vlen"].sum())
+    out = np.zeros(total + 1, np.uint8)
+    sizes = np.zeros(n + 1, np.uint64)
+    out_len = ctypes.c_uint64(0)
+    _lib.check(_lib.lib().nkv_encode_records(ctx.h, ctypes.byref(puts), out.ctypes.data, total, sizes.ctypes.data,
+                                             None, ctypes.byref(out_len)), "record encode")
+    return out[:out_len.value].tobytes(), sizes[:n].copy()
+
+
 def value_spans(stream: bytes, rec_sizes: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
     """Host reference for the value locator: (offset, length) of each Value."""
     offs = np.zeros(len(rec_sizes), np.uint64)
