@@ -22,7 +22,7 @@ SOURCES = ["kernels.hip", "crc.hip", "bloom.hip", "merge.hip", "memtable.hip", "
            "capi.cpp",
            "group.cpp", "host_stage.cpp"]
 HEADERS = ["internal.hpp", "context.hpp", "sha1_dev.hpp", "host_stage.hpp", "crc_dev.hpp", "murmur_dev.hpp",
-           "bytes_dev.hpp", "merge_copy_dev.hpp"]
+           "bytes_dev.hpp", "merge_copy_dev.hpp", "record_dev.hpp"]
 ARCH = os.environ.get("NKV_OFFLOAD_ARCH", "gfx950")
 FLAGS = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-shared", "-pthread",
          "-Wall", "-Wno-unused-result"]

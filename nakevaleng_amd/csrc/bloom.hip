@@ -18,22 +18,16 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "internal.hpp"
+#include "internal.hpp"  // record_dev.hpp: header_in, ld_le64, kHdr, kAtKeySize
 #include "murmur_dev.hpp"  // mm_states, mm_fmix, fastmod_u32, kBloomMaxK
 
 namespace nkv {
 
 constexpr int kBloomBlock = 256;
 
-__device__ __forceinline__ uint64_t bl_ld_le64(const uint8_t* p) {
-    uint64_t v = 0;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) v |= uint64_t(p[i]) << (8 * i);
-    return v;
-}
-
 // MODE 0: key i at base + off[i], len[i].  MODE 1: key of the record at
-// base + off[i] (at +30, KeySize at +14), checked against stream_len (err).
+// base + off[i], its span checked against stream_len (err; the check is
+// record_dev.hpp's key span, written out here).
 // QUERY: out[i] = every bit set; else set the bits.
 template <int MODE, bool QUERY>
 __global__ __launch_bounds__(kBloomBlock) void k_bloom(const uint8_t* __restrict__ base,
@@ -55,12 +49,12 @@ __global__ __launch_bounds__(kBloomBlock) void k_bloom(const uint8_t* __restrict
             atomicOr(err, 1u);
             return;
         }
-        L = bl_ld_le64(base + r + 14);
-        if (L > stream_len - r - 30) {
+        L = ld_le64(base + r + kAtKeySize);
+        if (L > stream_len - r - kHdr) {
             atomicOr(err, 1u);
             return;
         }
-        key = base + r + 30;
+        key = base + r + kHdr;
     }
     bool hit = true;
     for (uint32_t j0 = 0; j0 < k; j0 += kBloomMaxK) {
@@ -103,9 +97,9 @@ __device__ __forceinline__ bool bloom_key(const uint8_t* base, const uint64_t* o
     }
     const uint64_t r = off[i];
     if (!header_in(r, stream_len)) return false;
-    const uint64_t l = bl_ld_le64(base + r + 14);
-    if (l > stream_len - r - 30) return false;
-    *key = base + r + 30;
+    const uint64_t l = ld_le64(base + r + kAtKeySize);
+    if (l > stream_len - r - kHdr) return false;
+    *key = base + r + kHdr;
     *L = l;
     return true;
 }

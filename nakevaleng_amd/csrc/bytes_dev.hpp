@@ -1,31 +1,15 @@
-// bytes_dev.hpp -- helpers of the record kernels (merge.hip, index.hip,
-// lookup.hip): fields and keys at any alignment, 16 source bytes at any
-// alignment out of aligned 16-byte loads, and a workgroup's search in an
-// ascending array.
+// bytes_dev.hpp -- byte movers and searches of the record kernels (merge.hip,
+// memtable.hip, index.hip, lookup.hip, encode.hip and merge_copy_dev.hpp): 16
+// source bytes at any alignment out of aligned 16-byte loads, searches in an
+// ascending array by one lane and by a workgroup, and the scan's total.  The
+// record format itself and the key order are record_dev.hpp's.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "internal.hpp"  // kBlock
+#include "internal.hpp"  // kBlock; record_dev.hpp
 
 namespace nkv {
-
-__device__ __forceinline__ uint64_t ld_le64(const uint8_t* p) {  // any alignment
-    uint64_t v = 0;
-#pragma unroll
-    for (int b = 0; b < 8; ++b) v |= uint64_t(p[b]) << (8 * b);
-    return v;
-}
-
-// bytes.Compare: unsigned lexicographic, a proper prefix sorts first
-__device__ inline int cmp_bytes(const uint8_t* a, uint64_t la, const uint8_t* b, uint64_t lb) {
-    const uint64_t m = la < lb ? la : lb;
-    for (uint64_t i = 0; i < m; ++i) {
-        const uint8_t x = a[i], y = b[i];
-        if (x != y) return x < y ? -1 : 1;
-    }
-    return la < lb ? -1 : (la > lb ? 1 : 0);
-}
 
 __device__ __forceinline__ uint32_t sel4(uint32_t q, uint32_t a, uint32_t b, uint32_t c, uint32_t d) {
     return q == 0 ? a : (q == 1 ? b : (q == 2 ? c : d));
@@ -75,6 +59,18 @@ __device__ __forceinline__ uint4 ld_piece(uint64_t S, uint32_t cnt, uint32_t d) 
     return v;
 }
 
+// The last index j in [lo, hi) with a[j] <= x; a ascending, a[lo] <= x.  The
+// index type is the caller's: 32 bits where the array is a list in LDS.
+template <class A, class I>
+__device__ __forceinline__ I last_at_most(const A& a, I lo, I hi, uint64_t x) {
+    while (hi - lo > 1) {
+        const I mid = lo + (hi - lo) / 2;
+        if (a[mid] <= x) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
 // The first index in [lo, hi) with a[index] >= key (hi if none), a ascending,
 // found by the whole workgroup: every lane probes one of kBlock evenly spaced
 // places and the count of probes below the key picks the gap between two of
@@ -92,6 +88,16 @@ __device__ __forceinline__ uint64_t first_at_least(const uint64_t* __restrict__ 
         hi = next < hi ? next : hi;
     }
     return lo;
+}
+
+// Behind an exclusive scan of n sizes into off: off[n] = the total, and the
+// total next to the error word for the host.  A template, so that only the
+// translation units that launch it carry a copy.
+template <class T>
+__global__ void k_scan_total(const T* __restrict__ size, T* __restrict__ off, uint64_t n, T* __restrict__ total) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    off[n] = off[n - 1] + size[n - 1];
+    *total = off[n];
 }
 
 }  // namespace nkv

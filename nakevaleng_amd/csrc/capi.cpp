@@ -82,14 +82,49 @@ int grow_host(nkv_ctx* c, size_t bytes) {
 
 uint64_t align16(uint64_t x) { return (x + 15) & ~uint64_t(15); }
 
-// sum(rec_size) <= stream_len, checked term by term so a wrapped sum cannot pass
-bool records_fit(const uint64_t* rec_size, uint64_t n, uint64_t stream_len) {
-    uint64_t left = stream_len;
+// What the n sizes leave of stream_len, taken off term by term so a wrapped
+// sum cannot pass; false if they do not fit.
+static bool records_left(const uint64_t* rec_size, uint64_t n, uint64_t stream_len, uint64_t* left) {
+    *left = stream_len;
     for (uint64_t i = 0; i < n; ++i) {
-        if (rec_size[i] > left) return false;
-        left -= rec_size[i];
+        if (rec_size[i] > *left) return false;
+        *left -= rec_size[i];
     }
     return true;
+}
+
+bool records_fit(const uint64_t* rec_size, uint64_t n, uint64_t stream_len) {
+    uint64_t left;
+    return records_left(rec_size, n, stream_len, &left);
+}
+
+bool records_fill(const uint64_t* rec_size, uint64_t n, uint64_t stream_len) {
+    uint64_t left;
+    return records_left(rec_size, n, stream_len, &left) && left == 0;
+}
+
+int read_verdict(nkv_ctx* c, const unsigned int* d_err) {
+    unsigned int h = 0;
+    HIPTRY(hipMemcpyAsync(&h, d_err, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPTRY(hipStreamSynchronize(c->stream));
+    return h ? NKV_ERR_INVALID : NKV_OK;
+}
+
+int upload_records(nkv_ctx* c, const uint8_t* stream, uint64_t stream_len, const uint64_t* rec_size, uint64_t n,
+                   void* d_stream, uint64_t* d_size, uint64_t* d_off) {
+    HIPTRY(hipMemcpyAsync(d_stream, stream, stream_len, hipMemcpyHostToDevice, c->stream));
+    HIPTRY(hipMemcpyAsync(d_size, rec_size, 8 * n, hipMemcpyHostToDevice, c->stream));
+    return nkv_record_offsets_dev(c, d_size, n, d_off);
+}
+
+int download_table(nkv_ctx* c, const void* d_table, uint64_t len, const uint64_t* d_off, uint64_t n, uint8_t* out,
+                   uint64_t* out_rec_size) {
+    std::vector<uint64_t> off(n);
+    HIPTRY(hipMemcpyAsync(out, d_table, len, hipMemcpyDeviceToHost, c->stream));
+    HIPTRY(hipMemcpyAsync(off.data(), d_off, 8 * n, hipMemcpyDeviceToHost, c->stream));
+    HIPTRY(hipStreamSynchronize(c->stream));
+    for (uint64_t j = 0; j < n; ++j) out_rec_size[j] = (j + 1 < n ? off[j + 1] : len) - off[j];
+    return NKV_OK;
 }
 
 // The pinned block (nkv_host_alloc on this context) that holds every value
@@ -1432,10 +1467,7 @@ int nkv_tree_from_records(nkv_ctx* c, const uint8_t* stream, uint64_t stream_len
     TRY(grow(c->d_err, 4));
     unsigned int* err = static_cast<unsigned int*>(c->d_err.p);
     TRY(records_tree(c, static_cast<const uint8_t*>(c->d_data.p), stream_len, rec_off, n, nodes, err));
-    unsigned int h = 0;
-    HIPTRY(hipMemcpyAsync(&h, err, 4, hipMemcpyDeviceToHost, c->stream));
-    HIPTRY(hipStreamSynchronize(c->stream));
-    if (h) return NKV_ERR_INVALID;
+    TRY(read_verdict(c, err));
     return finish_tree(c, nodes, n, root20, nodes_out, img_out);
 } NKV_CATCH
 
@@ -1637,10 +1669,7 @@ int nkv_locate_values_dev(nkv_ctx* c, const void* d_stream, uint64_t stream_len,
     TRY(locate_parts(c, n, &part));
     HIPTRY(launch_locate(static_cast<const uint8_t*>(d_stream), stream_len, d_rec_off, n, d_voff,
                          d_vlen, err, nullptr, part, c->stream));
-    unsigned int h = 0;
-    HIPTRY(hipMemcpyAsync(&h, err, 4, hipMemcpyDeviceToHost, c->stream));
-    HIPTRY(hipStreamSynchronize(c->stream));
-    return h ? NKV_ERR_INVALID : NKV_OK;
+    return read_verdict(c, err);
 } NKV_CATCH
 
 int nkv_tree_from_records_dev(nkv_ctx* c, const void* d_stream, uint64_t stream_len, const uint64_t* d_rec_off,
@@ -1657,10 +1686,7 @@ int nkv_tree_from_records_dev(nkv_ctx* c, const void* d_stream, uint64_t stream_
     TRY(records_tree(c, static_cast<const uint8_t*>(d_stream), stream_len, d_rec_off, n,
                      static_cast<uint8_t*>(d_nodes), err));
     if (d_err) return NKV_OK;
-    unsigned int h = 0;
-    HIPTRY(hipMemcpyAsync(&h, err, 4, hipMemcpyDeviceToHost, c->stream));
-    HIPTRY(hipStreamSynchronize(c->stream));
-    return h ? NKV_ERR_INVALID : NKV_OK;
+    return read_verdict(c, err);
 } NKV_CATCH
 
 // Compaction read in one pass: the Merkle tree of the records' Values and the
@@ -1789,10 +1815,7 @@ int nkv_bloom_insert_records_dev(nkv_ctx* c, const void* d_stream, uint64_t stre
     HIPTRY(hipMemsetAsync(err, 0, 4, c->stream));
     TRY(bloom_insert(c, 1, static_cast<const uint8_t*>(d_stream), d_rec_off, nullptr, stream_len, n, m, k, seed0,
                      static_cast<uint32_t*>(d_bits), err));
-    unsigned int h = 0;
-    HIPTRY(hipMemcpyAsync(&h, err, 4, hipMemcpyDeviceToHost, c->stream));
-    HIPTRY(hipStreamSynchronize(c->stream));
-    return h ? NKV_ERR_INVALID : NKV_OK;
+    return read_verdict(c, err);
 } NKV_CATCH
 
 int nkv_bloom_query_dev(nkv_ctx* c, const void* d_keys, const uint64_t* d_off, const uint64_t* d_len, uint64_t n,

@@ -127,6 +127,25 @@ struct DevBuf {
 // Grow a device scratch buffer (contents are not kept).
 int grow(DevBuf& b, size_t bytes);
 
+// Bump-pointer carver of a scratch buffer.  An entry names its arrays in one
+// sequence of take() calls and runs it twice: over no buffer, where bytes()
+// is what grow() receives, and over the grown buffer, where the same calls
+// hand out the pointers -- the size and the pointers cannot disagree.
+struct Carver {
+    uint8_t* base = nullptr;  // nullptr: measuring
+    uint64_t at = 0;
+    explicit Carver(void* p = nullptr) : base(static_cast<uint8_t*>(p)) {}
+    // count elements of T at the next multiple of align
+    template <class T>
+    T* take(uint64_t count, uint64_t align = alignof(T)) {
+        at = (at + align - 1) & ~(align - 1);
+        T* p = base ? reinterpret_cast<T*>(base + at) : nullptr;
+        at += count * sizeof(T);
+        return p;
+    }
+    uint64_t bytes() const { return at; }
+};
+
 }  // namespace nkv
 
 // ---------------------------------------------------------------------------
@@ -248,6 +267,21 @@ int tree_from_device_values(nkv_ctx* c, const uint8_t* base, const uint64_t* off
 int finish_tree(nkv_ctx* c, uint8_t* nodes, uint64_t n, uint8_t* root20, uint8_t* nodes_out, uint8_t* img_out);
 // Record events around the leaf kernel and the reduce (which = 0, 1, 2).
 int mark(nkv_ctx* c, int which);
+// The verdict of a validating kernel: the error word to the host and the
+// stream synchronized; NKV_ERR_INVALID if the word is set.
+int read_verdict(nkv_ctx* c, const unsigned int* d_err);
+// The n sizes fit the stream (their sum <= stream_len) / add up to it exactly;
+// term by term, so a wrapped sum cannot pass.
+bool records_fit(const uint64_t* rec_size, uint64_t n, uint64_t stream_len);
+bool records_fill(const uint64_t* rec_size, uint64_t n, uint64_t stream_len);
+// A host stream and its n record sizes to d_stream / d_size, and the records'
+// offsets made on the device into d_off (nkv_record_offsets_dev).
+int upload_records(nkv_ctx* c, const uint8_t* stream, uint64_t stream_len, const uint64_t* rec_size, uint64_t n,
+                   void* d_stream, uint64_t* d_size, uint64_t* d_off);
+// A written table of n records and len bytes to the host (synchronizes):
+// its bytes to out, and its offsets d_off as sizes to out_rec_size.
+int download_table(nkv_ctx* c, const void* d_table, uint64_t len, const uint64_t* d_off, uint64_t n, uint8_t* out,
+                   uint64_t* out_rec_size);
 // Events bracketing a host-buffer call (which = 0 before the upload, 1 after the download).
 int host_mark(nkv_ctx* c, int which);
 

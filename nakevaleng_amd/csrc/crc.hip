@@ -34,7 +34,7 @@
 #include <algorithm>
 
 #include "crc_dev.hpp"
-#include "internal.hpp"
+#include "internal.hpp"  // record_dev.hpp: header_in, ld_le64, kHdr, kAt*
 
 namespace nkv {
 
@@ -78,13 +78,6 @@ __device__ __forceinline__ uint32_t lane_byte(uint32_t crc, uint32_t b, uint32_t
     uint32_t t = lane_lut<0, 0>((crc ^ b) & 0xFFu, la0);
     asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(t));
     return t ^ (crc >> 8);
-}
-
-__device__ __forceinline__ uint64_t crc_ld_le64(const uint8_t* p) {
-    uint64_t v = 0;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) v |= uint64_t(p[i]) << (8 * i);
-    return v;
 }
 
 // Crc, KeySize, ValueSize of the record header at p (record.go:191-199: Crc at
@@ -281,8 +274,8 @@ __global__ __launch_bounds__(kCrcLanesWG) void k_crc_lanes(const uint8_t* __rest
             crc_header(rec, stored, ks, vs);
             if (!hin) {
                 hdr_bad = live;
-            } else if (ks <= stream_len && vs <= stream_len && r + 30 + ks + vs <= stream_len) {
-                s = base + r + 30;
+            } else if (ks <= stream_len && vs <= stream_len && r + kHdr + ks + vs <= stream_len) {
+                s = base + r + kHdr;
                 L = ks + vs;
             } else {
                 hdr_bad = true;
@@ -445,10 +438,10 @@ __global__ __launch_bounds__(WG) void k_crc_group(const uint8_t* __restrict__ ba
             if (RECORDS) {
                 const uint64_t r = off[i];
                 if (header_in(r, stream_len)) {
-                    const uint64_t ks = crc_ld_le64(base + r + 14);
-                    const uint64_t vs = crc_ld_le64(base + r + 22);
-                    if (ks <= stream_len && vs <= stream_len && r + 30 + ks + vs <= stream_len) {
-                        s = base + r + 30;
+                    const uint64_t ks = ld_le64(base + r + kAtKeySize);
+                    const uint64_t vs = ld_le64(base + r + kAtValueSize);
+                    if (ks <= stream_len && vs <= stream_len && r + kHdr + ks + vs <= stream_len) {
+                        s = base + r + kHdr;
                         L = ks + vs;
                         stored = uint32_t(base[r]) | uint32_t(base[r + 1]) << 8 | uint32_t(base[r + 2]) << 16 |
                                  uint32_t(base[r + 3]) << 24;

@@ -14,9 +14,9 @@
 //                    its key and its value.  Nothing follows an offset before
 //                    the host has read this kernel's verdict.
 //   scan             exclusive sums of the sizes = the record offsets, and
-//                    k_encode_total puts the total behind them (n + 1 entries)
+//                    k_scan_total puts the total behind them (n + 1 entries)
 //                    and next to the error word; the host reads both once.
-//   k_encode_write   tiles the OUTPUT bytes as k_merge_copy and k_value_copy do:
+//   k_encode_write   tiles the OUTPUT bytes as the other writer kernels do:
 //                    a workgroup owns 16 KiB of d_out on the 16-byte grid of
 //                    its address and every lane stores one aligned uint4 per
 //                    step.  A record is three pieces: its 30 header bytes, made
@@ -39,16 +39,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <vector>
-
-#include "bytes_dev.hpp"  // ld16_any, ld_piece, funnel16, first_at_least
+#include "bytes_dev.hpp"  // ld16_any, ld_piece, funnel16, first_at_least, last_at_most, k_scan_total
 #include "context.hpp"
 
 using namespace nkv;
 
 namespace {
 
-constexpr uint32_t kHdr = 30;  // record.go:191-199: Crc 4 | Timestamp 8 | Status 1 | TypeInfo 1 | KeySize 8 | ValueSize 8
 constexpr uint32_t kCopyTile = 16384;  // output bytes per workgroup
 constexpr uint32_t kCopyChunk = 16;    // output bytes per lane and step
 // records that can overlap one tile: at most kCopyTile / kHdr + 2 = 548 (the
@@ -95,24 +92,6 @@ __global__ __launch_bounds__(kBlock) void k_encode_measure(Puts P, uint32_t n, S
     if (!ok) atomicOr(err, 1u);
 }
 
-// off[n] = the total, next to the error word for the host
-__global__ void k_encode_total(const uint64_t* __restrict__ size, uint64_t* __restrict__ off, uint64_t n,
-                               uint64_t* __restrict__ total) {
-    if (blockIdx.x != 0 || threadIdx.x != 0) return;
-    off[n] = off[n - 1] + size[n - 1];
-    *total = off[n];
-}
-
-// The last index j in [lo, hi) with a[j] <= x; a ascending, a[lo] <= x.
-__device__ __forceinline__ uint32_t last_at_most(const uint64_t* a, uint32_t lo, uint32_t hi, uint64_t x) {
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) / 2;
-        if (a[mid] <= x) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
-
 // The header fields of one record.
 struct Head {
     uint64_t ts, kl, vl;
@@ -121,12 +100,12 @@ struct Head {
 
 // Byte r (0 <= r < 30) of the header, Crc bytes 0.
 __device__ __forceinline__ uint32_t head_byte(const Head& h, uint32_t r) {
-    if (r < 4) return 0;
-    if (r < 12) return uint32_t(h.ts >> (8 * (r - 4))) & 0xFFu;
-    if (r == 12) return h.st;
-    if (r == 13) return h.ty;
-    if (r < 22) return uint32_t(h.kl >> (8 * (r - 14))) & 0xFFu;
-    return uint32_t(h.vl >> (8 * (r - 22))) & 0xFFu;
+    if (r < kAtTimestamp) return 0;
+    if (r < kAtStatus) return uint32_t(h.ts >> (8 * (r - kAtTimestamp))) & 0xFFu;
+    if (r == kAtStatus) return h.st;
+    if (r == kAtTypeInfo) return h.ty;
+    if (r < kAtValueSize) return uint32_t(h.kl >> (8 * (r - kAtKeySize))) & 0xFFu;
+    return uint32_t(h.vl >> (8 * (r - kAtValueSize))) & 0xFFu;
 }
 
 // Bytes 0 .. cnt - 1 of v kept, the rest zero, placed d bytes up (1 <= cnt <=
@@ -215,7 +194,7 @@ __global__ __launch_bounds__(kBlock) void k_encode_write(uint8_t* __restrict__ o
         if (p + kCopyChunk <= head || p >= pend) continue;
         const uint64_t ob = p > head ? p - head : 0;  // first output byte of the chunk
         const bool whole = p >= head && p + kCopyChunk <= pend;
-        const uint32_t e = last_at_most(l_off, 0, cnt, ob);  // the record that holds ob
+        const uint32_t e = last_at_most(l_off, 0u, cnt, ob);  // the record that holds ob
         const uint64_t a = l_off[e], b = l_off[e + 1], kl = l_kl[e];
         const uint64_t r0 = ob - a;
         const bool in_key = r0 >= kHdr && r0 + kCopyChunk <= kHdr + kl;
@@ -249,7 +228,7 @@ __global__ __launch_bounds__(kBlock) void k_encode_write(uint8_t* __restrict__ o
         const uint64_t p = p0 + uint64_t(it * kBlock + threadIdx.x) * kCopyChunk;
         const uint64_t ob = p > head ? p - head : 0;
         const bool whole = p >= head && p + kCopyChunk <= pend;
-        uint32_t e = last_at_most(l_off, 0, cnt, ob);
+        uint32_t e = last_at_most(l_off, 0u, cnt, ob);
         uint64_t a = l_off[e], b = l_off[e + 1], kl = l_kl[e];
         if (whole) {  // the pieces that overlap the chunk, in registers
             uint4 acc = make_uint4(0, 0, 0, 0);
@@ -319,8 +298,6 @@ __global__ __launch_bounds__(kBlock) void k_encode_patch(uint8_t* __restrict__ o
     if (crc_out) crc_out[g] = v;
 }
 
-inline unsigned blocks_for(uint64_t n) { return unsigned((n + kBlock - 1) / kBlock); }
-
 // What both forms refuse before anything is launched or copied.
 int check_puts(const nkv_puts* u, const uint64_t* out_len) {
     if (!u || !out_len || u->n > kMaxN) return NKV_ERR_INVALID;
@@ -355,11 +332,20 @@ int nkv_encode_records_dev(nkv_ctx* c, const nkv_puts* puts, void* d_out, uint64
     // scratch in d_stmp, which carries nothing from call to call: sizes (n),
     // payload lengths (n), offsets (n + 1), key and value addresses (n each),
     // checksums (n u32)
-    TRY(grow(c->d_stmp, 8 * (5 * n + 1) + 4 * n));
-    uint64_t* a = static_cast<uint64_t*>(c->d_stmp.p);
-    const Spans S{a, a + n, a + 3 * n + 1, a + 4 * n + 1};
-    uint64_t* off = a + 2 * n;
-    uint32_t* crc = reinterpret_cast<uint32_t*>(a + 5 * n + 1);
+    Spans S;
+    uint64_t* off;
+    uint32_t* crc;
+    const auto carve = [&](Carver k) {
+        S.size = k.take<uint64_t>(n);
+        S.plen = k.take<uint64_t>(n);
+        off = k.take<uint64_t>(n + 1);
+        S.ksrc = k.take<uint64_t>(n);
+        S.vsrc = k.take<uint64_t>(n);
+        crc = k.take<uint32_t>(n);
+        return k.bytes();
+    };
+    TRY(grow(c->d_stmp, carve(Carver())));
+    carve(Carver(c->d_stmp.p));
     size_t tb = 0;
     HIPTRY(scan_exclusive_u64(S.size, off, n, nullptr, &tb, c->stream));
     TRY(grow(c->d_tmp, tb));
@@ -375,7 +361,7 @@ int nkv_encode_records_dev(nkv_ctx* c, const nkv_puts* puts, void* d_out, uint64
     hipLaunchKernelGGL(k_encode_measure, dim3(blocks_for(n)), dim3(kBlock), 0, c->stream, P, uint32_t(n), S, err);
     HIPTRY(hipGetLastError());
     HIPTRY(scan_exclusive_u64(S.size, off, n, c->d_tmp.p, &tb, c->stream));
-    hipLaunchKernelGGL(k_encode_total, dim3(1), dim3(1), 0, c->stream, S.size, off, n, total);
+    hipLaunchKernelGGL(k_scan_total<uint64_t>, dim3(1), dim3(1), 0, c->stream, S.size, off, n, total);
     HIPTRY(hipGetLastError());
     // the verdict and the length, before anything is written
     uint64_t h[2] = {0, 0};
@@ -461,13 +447,8 @@ int nkv_encode_records(nkv_ctx* c, const nkv_puts* puts, uint8_t* out, uint64_t 
     uint32_t* d_crc = static_cast<uint32_t*>(c->d_len.p);
     uint64_t got = 0;
     TRY(nkv_encode_records_dev(c, &dp, c->d_nodes.p, total, d_out_off, d_crc, &got));
-    std::vector<uint64_t> off(n);
-    HIPTRY(hipMemcpyAsync(out, c->d_nodes.p, total, hipMemcpyDeviceToHost, c->stream));
-    HIPTRY(hipMemcpyAsync(off.data(), d_out_off, 8 * n, hipMemcpyDeviceToHost, c->stream));
     if (crc_out) HIPTRY(hipMemcpyAsync(crc_out, d_crc, 4 * n, hipMemcpyDeviceToHost, c->stream));
-    HIPTRY(hipStreamSynchronize(c->stream));
-    for (uint64_t i = 0; i < n; ++i) out_rec_size[i] = (i + 1 < n ? off[i + 1] : total) - off[i];
-    return NKV_OK;
+    return download_table(c, c->d_nodes.p, total, d_out_off, n, out, out_rec_size);  // the call's synchronize
 } NKV_CATCH
 
 }  // extern "C"

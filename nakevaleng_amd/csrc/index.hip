@@ -10,7 +10,7 @@
 //
 // Stages, all on the context's stream:
 //   k_index_measure   one lane per record: the header lies in the stream and so
-//                     does the key; writes 16 + KeySize as the Index entry's
+//                     does the key (record_dev.hpp key_span_in); writes 16 + KeySize as the Index entry's
 //                     size and, for a selected record, as its Summary entry's.
 //                     Selected entry e is record e * page, the last entry the
 //                     last record: a closed form, so no compaction pass.
@@ -27,14 +27,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "bytes_dev.hpp"  // ld_le64, sel4, first_at_least
+#include "bytes_dev.hpp"  // sel4, first_at_least
 #include "context.hpp"
 
 using namespace nkv;
 
 namespace {
 
-constexpr int kHdr = 30;  // record.go:191-199: Crc 4 | Timestamp 8 | Status 1 | TypeInfo 1 | KeySize 8 | ValueSize 8
 constexpr uint32_t kEnt = 16;           // KeySize + Offset in front of every entry's key
 constexpr uint32_t kWriteTile = 16384;  // image bytes per workgroup
 constexpr uint32_t kWriteChunk = 16;    // image bytes per lane and step
@@ -53,16 +52,8 @@ __global__ __launch_bounds__(kBlock) void k_index_measure(const uint8_t* __restr
                                                           uint64_t* __restrict__ ssz, unsigned int* err) {
     const uint64_t i = uint64_t(blockIdx.x) * kBlock + threadIdx.x;
     if (i >= n) return;
-    const uint64_t o = off[i];
-    bool bad = !header_in(o, L);
     uint64_t ks = 0;
-    if (!bad) {
-        ks = ld_le64(s + o + 14);
-        if (ks > L - o - kHdr) {  // the key span [o + 30, o + 30 + ks) leaves the stream
-            bad = true;
-            ks = 0;
-        }
-    }
+    const bool bad = !key_span_in(s, L, off[i], &ks);  // ks stays 0
     isz[i] = kEnt + ks;
     if (i == n - 1) ssz[m - 1] = kEnt + ks;
     else if (i % page == 0) ssz[i / page] = kEnt + ks;
@@ -201,8 +192,6 @@ __global__ __launch_bounds__(kBlock) void k_summary_header(uint8_t* __restrict__
     }
 }
 
-inline unsigned blocks_for(uint64_t n) { return unsigned((n + kBlock - 1) / kBlock); }
-
 uint64_t summary_entries(uint64_t n, uint64_t page) {
     if (n <= 1) return n;
     if (page == 0) return 0;
@@ -240,9 +229,16 @@ int index_summary(nkv_ctx* c, const uint8_t* d_stream, uint64_t stream_len, cons
 
     // scratch in d_stmp, which carries nothing from call to call: the Index
     // entries' sizes and offsets (n each), the Summary entries' (m each)
-    TRY(grow(c->d_stmp, 8 * (2 * n + 2 * m)));
-    uint64_t* a = static_cast<uint64_t*>(c->d_stmp.p);
-    uint64_t *isz = a, *ioff = a + n, *ssz = a + 2 * n, *soff = a + 2 * n + m;
+    uint64_t *isz, *ioff, *ssz, *soff;
+    const auto carve = [&](Carver k) {
+        isz = k.take<uint64_t>(n);
+        ioff = k.take<uint64_t>(n);
+        ssz = k.take<uint64_t>(m);
+        soff = k.take<uint64_t>(m);
+        return k.bytes();
+    };
+    TRY(grow(c->d_stmp, carve(Carver())));
+    carve(Carver(c->d_stmp.p));
     size_t tb = 0;
     HIPTRY(scan_exclusive_u64(isz, ioff, n, nullptr, &tb, c->stream));
     TRY(grow(c->d_tmp, tb));
@@ -332,12 +328,7 @@ int nkv_index_summary_from_records(nkv_ctx* c, const uint8_t* stream, uint64_t s
     *index_len = 0;
     *summary_len = 0;
     if (n > kMaxN || (n && (!stream || !rec_size))) return NKV_ERR_INVALID;
-    uint64_t left = stream_len;  // the sizes add up to the stream exactly, term by term (no wrapped sum)
-    for (uint64_t i = 0; i < n; ++i) {
-        if (rec_size[i] > left) return NKV_ERR_INVALID;
-        left -= rec_size[i];
-    }
-    if (left != 0) return NKV_ERR_INVALID;
+    if (!records_fill(rec_size, n, stream_len)) return NKV_ERR_INVALID;
     const bool query = !index_out && !summary_out;
     const uint8_t* d_stream = nullptr;
     const uint64_t* d_off = nullptr;
@@ -345,9 +336,8 @@ int nkv_index_summary_from_records(nkv_ctx* c, const uint8_t* stream, uint64_t s
         TRY(grow(c->d_data, stream_len));
         TRY(grow(c->d_len, 8 * n));
         TRY(grow(c->d_off, 8 * n));
-        HIPTRY(hipMemcpyAsync(c->d_data.p, stream, stream_len, hipMemcpyHostToDevice, c->stream));
-        HIPTRY(hipMemcpyAsync(c->d_len.p, rec_size, 8 * n, hipMemcpyHostToDevice, c->stream));
-        TRY(nkv_record_offsets_dev(c, static_cast<const uint64_t*>(c->d_len.p), n, static_cast<uint64_t*>(c->d_off.p)));
+        TRY(upload_records(c, stream, stream_len, rec_size, n, c->d_data.p, static_cast<uint64_t*>(c->d_len.p),
+                           static_cast<uint64_t*>(c->d_off.p)));
         d_stream = static_cast<const uint8_t*>(c->d_data.p);
         d_off = static_cast<const uint64_t*>(c->d_off.p);
     }

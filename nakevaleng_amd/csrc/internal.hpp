@@ -1,11 +1,16 @@
-// internal.hpp -- launcher declarations shared by kernels.hip and capi.cpp.
+// internal.hpp -- the constants and launcher declarations shared by the device
+// translation units (*.hip) and the C-ABI ones (capi.cpp, group.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "record_dev.hpp"  // header_in
+
 namespace nkv {
 
 constexpr int kBlock = 256;       // threads per workgroup = leaves per K1 block
+// workgroups of kBlock lanes for one lane per item
+inline unsigned blocks_for(uint64_t n) { return unsigned((n + kBlock - 1) / kBlock); }
 constexpr int kSlabLevels = 8;    // log2(kBlock): levels one k_reduce workgroup builds
 // levels of at least this many nodes are reduced two at a time at full lane
 // use (k_reduce2) before the slabs take over (launch_reduce)
@@ -20,10 +25,6 @@ constexpr int kLeafWavesPerSimd = 8;  // 8 waves/SIMD <=> <= 64 VGPRs
 // read-back): range = the batch's (min, max) full-block counts from
 // launch_len_range; pol 1 runs the kernel only for a narrow range (input
 // order), pol 2 only for a wide one (length-sorted work queue), 0 always.
-// A record header [r, r + 30) (record.go:191-199) lies inside a stream of len
-// bytes; written so that a wild offset near 2^64 cannot wrap past the check.
-__host__ __device__ inline bool header_in(uint64_t r, uint64_t len) { return r <= len && len - r >= 30; }
-
 struct Gate {
     const unsigned int* range = nullptr;
     int pol = 0;

@@ -2534,12 +2534,11 @@ hipError_t launch_small_service(SmallMailbox* mb, const SmallMailbox* rb, const 
     return hipGetLastError();
 }
 
-static inline unsigned grid_for(uint64_t n) { return unsigned((n + kBlock - 1) / kBlock); }
 
 template <int MODE, int LOAD>
 static void leaf_kernel(const uint8_t* base, const uint64_t* off, const uint64_t* len, uint64_t stride, uint64_t L,
                         const uint32_t* perm, uint64_t n, uint8_t* nodes, hipStream_t s, Gate gate) {
-    hipLaunchKernelGGL((k_leaf<MODE, LOAD>), dim3(grid_for(n)), dim3(kBlock), 0, s, base, off, len, stride, L,
+    hipLaunchKernelGGL((k_leaf<MODE, LOAD>), dim3(blocks_for(n)), dim3(kBlock), 0, s, base, off, len, stride, L,
                        perm, n, nodes, gate);
 }
 
@@ -2570,7 +2569,7 @@ hipError_t launch_leaf_verify(const uint8_t* stream, uint64_t stream_len, const 
                               int policy, uint64_t* voff, uint64_t* vlen, uint8_t* nodes, uint32_t* crc_out,
                               unsigned long long* stats, unsigned int* range, uint32_t* part, hipStream_t s,
                               uint32_t* flags, uint32_t* flags_next) {
-    const unsigned nb = grid_for(n);
+    const unsigned nb = blocks_for(n);
     if (policy == 0) flags = nullptr;
     hipLaunchKernelGGL(k_leaf_verify, dim3(nb), dim3(kBlock), 0, s, stream, stream_len, rec_off, n, policy, voff,
                        vlen, nodes, crc_out, flags ? reinterpret_cast<unsigned long long*>(flags + 4) : stats,
@@ -2633,7 +2632,7 @@ hipError_t launch_reduce(uint8_t* nodes, uint64_t n, int from_level, int top, hi
             j0 = jmax;
         } else {
             const int jmax = (j0 + kSlabLevels < top) ? j0 + kSlabLevels : top;
-            hipLaunchKernelGGL(k_reduce<kBlock>, dim3(grid_for(cnt)), dim3(kBlock), 0, s, nodes, n, j0, jmax, gate);
+            hipLaunchKernelGGL(k_reduce<kBlock>, dim3(blocks_for(cnt)), dim3(kBlock), 0, s, nodes, n, j0, jmax, gate);
             j0 = jmax;
         }
         hipError_t e = hipGetLastError();
@@ -2651,12 +2650,12 @@ hipError_t launch_bfs_image(const uint8_t* nodes, const BfsLayout& lay, uint8_t*
 }
 
 // one (lo, hi, flag) triple per workgroup (k_locate, k_leaf_records)
-uint64_t locate_part_words(uint64_t n) { return 3 * uint64_t(grid_for(n)); }
+uint64_t locate_part_words(uint64_t n) { return 3 * uint64_t(blocks_for(n)); }
 
 hipError_t launch_locate(const uint8_t* stream, uint64_t stream_len, const uint64_t* rec_off,
                          uint64_t n, uint64_t* voff, uint64_t* vlen, unsigned int* err, unsigned int* range,
                          uint32_t* part, hipStream_t s) {
-    const unsigned nb = grid_for(n);
+    const unsigned nb = blocks_for(n);
     hipLaunchKernelGGL(k_locate, dim3(nb), dim3(kBlock), 0, s, stream, stream_len, rec_off, n, voff, vlen, part);
     hipLaunchKernelGGL(k_locate_fold, dim3(1), dim3(kBlock), 0, s, part, nb, err, range);
     return hipGetLastError();
@@ -2666,7 +2665,7 @@ hipError_t launch_leaf_records(const uint8_t* stream, uint64_t stream_len, const
                                int policy, uint64_t* voff, uint64_t* vlen, uint8_t* nodes, unsigned int* err,
                                unsigned int* range, uint32_t* part, hipStream_t s, uint32_t* flags,
                                uint32_t* flags_next) {
-    const unsigned nb = grid_for(n);
+    const unsigned nb = blocks_for(n);
     if (policy == 0) flags = nullptr;
     hipLaunchKernelGGL(k_leaf_records, dim3(nb), dim3(kBlock), 0, s, stream, stream_len, rec_off, n, policy, voff,
                        vlen, nodes, part, flags, flags_next);

@@ -13,11 +13,13 @@
 //                   test reads the keys of records 0 and n - 1, and a lower
 //                   bound over rec_off reads every probed key in place.  Keys
 //                   are compared by an 8-byte big-endian prefix first and byte
-//                   by byte only where the prefixes are equal.
+//                   by byte only where the prefixes are equal (record_dev.hpp
+//                   cmp_prefixed).
 //   k_value_measure one lane per query: the found record's Value span, checked
 //                   against its stream.
-//   scan            exclusive sums of the lengths = the packed offsets; the host
-//                   reads the total and the verdict before the copy is launched.
+//   scan            exclusive sums of the lengths = the packed offsets
+//                   (k_scan_total puts the total behind them); the host reads
+//                   the total and the verdict before the copy is launched.
 //   k_value_copy    tiles the OUTPUT bytes as k_merge_copy does: a workgroup
 //                   owns 16 KiB of d_out and every lane writes 16 destination-
 //                   aligned bytes per step, put together in registers from
@@ -36,7 +38,6 @@ using namespace nkv;
 
 namespace {
 
-constexpr int kHdr = 30;  // record.go:191-199: Crc 4 | Timestamp 8 | Status 1 | TypeInfo 1 | KeySize 8 | ValueSize 8
 constexpr uint64_t kNone = ~uint64_t(0);
 constexpr uint32_t kCopyTile = 16384;  // output bytes per workgroup
 constexpr uint32_t kCopyChunk = 16;    // output bytes per lane and step
@@ -59,12 +60,6 @@ struct Query {
     uint64_t pfx;  // first 8 key bytes, big-endian, zero-padded
 };
 
-__device__ __forceinline__ uint64_t prefix_of(const uint8_t* key, uint64_t len) {
-    uint64_t p = 0;
-    for (uint32_t b = 0; b < 8 && b < len; ++b) p |= uint64_t(key[b]) << (56 - 8 * b);
-    return p;
-}
-
 constexpr int kBad = 2;  // probe: the record's header or key span leaves the stream
 
 // bytes.Compare(query, key of record j): -1, 0, 1, or kBad.  Nothing outside
@@ -72,15 +67,10 @@ constexpr int kBad = 2;  // probe: the record's header or key span leaves the st
 __device__ __forceinline__ int probe(const Query& Q, const uint8_t* __restrict__ s, uint64_t L,
                                      const uint64_t* __restrict__ off, uint64_t j) {
     const uint64_t o = off[j];
-    if (!header_in(o, L)) return kBad;
-    const uint64_t ks = ld_le64(s + o + 14);
-    if (ks > L - o - kHdr) return kBad;
+    uint64_t ks;
+    if (!key_span_in(s, L, o, &ks)) return kBad;
     const uint8_t* rk = s + o + kHdr;
-    const uint64_t rp = prefix_of(rk, ks);
-    if (Q.pfx != rp) return Q.pfx < rp ? -1 : 1;
-    // equal padded prefixes: a key of at most 8 bytes is a prefix of the other
-    if (Q.len <= 8 || ks <= 8) return Q.len < ks ? -1 : (Q.len > ks ? 1 : 0);
-    return cmp_bytes(Q.key + 8, Q.len - 8, rk + 8, ks - 8);
+    return cmp_prefixed(Q.pfx, Q.len, Q.key + 8, key_prefix(rk, ks), ks, rk + 8);
 }
 
 // Filter.Query (bloomfilter.go:93-111): every one of the k bits set.
@@ -149,7 +139,7 @@ __global__ __launch_bounds__(kBlock) void k_lookup(Tables R, const uint8_t* __re
     Query Q;
     Q.key = keys + koff[i];
     Q.len = klen[i];
-    Q.pfx = prefix_of(Q.key, Q.len);
+    Q.pfx = key_prefix(Q.key, Q.len);
     uint64_t h = kNone;
     uint8_t st = NKV_GET_ABSENT;
     bool bad = false;
@@ -160,7 +150,7 @@ __global__ __launch_bounds__(kBlock) void k_lookup(Tables R, const uint8_t* __re
             sg = search(R, t, Q, &j, &bad);
             if (sg == NKV_STAGE_FOUND) {
                 h = (uint64_t(t) << 32) | j;
-                st = (R.stream[t][R.off[t][j] + 12] & 1) ? NKV_GET_TOMBSTONE : NKV_GET_LIVE;
+                st = (R.stream[t][R.off[t][j] + kAtStatus] & 1) ? NKV_GET_TOMBSTONE : NKV_GET_LIVE;
             }
         }
         if (stage && live) stage[i * uint64_t(R.T) + t] = uint8_t(sg);
@@ -185,41 +175,18 @@ __global__ __launch_bounds__(kBlock) void k_value_measure(Tables R, const uint64
         bool bad = t >= uint64_t(R.T) || j >= R.n[t < uint64_t(R.T) ? t : 0];
         if (!bad) {
             const uint8_t* s = R.stream[t];
-            const uint64_t L = R.len[t], o = R.off[t][j];
-            bad = !header_in(o, L);
+            const uint64_t o = R.off[t][j];
+            uint64_t ks, v;
+            bad = !record_span_in(s, R.len[t], o, &ks, &v);
             if (!bad) {
-                const uint64_t ks = ld_le64(s + o + 14), v = ld_le64(s + o + 22), room = L - o - kHdr;
-                if (ks > room || v > room - ks) {
-                    bad = true;
-                } else {
-                    vs = v;
-                    at = uint64_t(reinterpret_cast<uintptr_t>(s + o + kHdr + ks));
-                }
+                vs = v;
+                at = uint64_t(reinterpret_cast<uintptr_t>(s + o + kHdr + ks));
             }
         }
         if (bad) atomicOr(err, 1u);
     }
     len[i] = vs;
     src[i] = at;
-}
-
-// off[q] = the total, next to the error word for the host
-__global__ void k_value_total(const uint64_t* __restrict__ len, uint64_t* __restrict__ off, uint64_t q,
-                              uint64_t* __restrict__ total) {
-    if (blockIdx.x != 0 || threadIdx.x != 0) return;
-    off[q] = off[q - 1] + len[q - 1];
-    *total = off[q];
-}
-
-// The last index j in [lo, hi) with a[j] <= x; a ascending, a[lo] <= x.
-template <class A>
-__device__ __forceinline__ uint64_t last_at_most(const A& a, uint64_t lo, uint64_t hi, uint64_t x) {
-    while (hi - lo > 1) {
-        const uint64_t mid = lo + (hi - lo) / 2;
-        if (a[mid] <= x) lo = mid;
-        else hi = mid;
-    }
-    return lo;
 }
 
 // Output byte o is byte o - off[i] of the Value at src[i], for the i with
@@ -259,7 +226,7 @@ __global__ __launch_bounds__(kBlock) void k_value_copy(uint8_t* __restrict__ out
         const uint64_t ob = p > head ? p - head : 0;  // first output byte of the chunk
         const bool whole = p >= head && p + kCopyChunk <= pend;
         // e = the query that holds ob (index into the list, or jlo + e in the arrays)
-        const uint64_t e0 = listed ? last_at_most(l_off, 0, cnt, ob) : last_at_most(off, jlo, jhi + 1, ob) - jlo;
+        const uint64_t e0 = listed ? last_at_most(l_off, uint64_t(0), uint64_t(cnt), ob) : last_at_most(off, jlo, jhi + 1, ob) - jlo;
         const uint64_t off0 = listed ? l_off[e0] : off[jlo + e0];
         const uint64_t off1 = listed ? l_off[e0 + 1] : off[jlo + e0 + 1];
         const uint64_t src0 = listed ? l_src[e0] : src[jlo + e0];
@@ -301,8 +268,6 @@ __global__ __launch_bounds__(kBlock) void k_value_copy(uint8_t* __restrict__ out
         }
     }
 }
-
-inline unsigned blocks_for(uint64_t n) { return unsigned((n + kBlock - 1) / kBlock); }
 
 // The tables as the kernels take them; NKV_ERR_INVALID for what the header refuses.
 int pack_tables(const nkv_lookup_table* tables, int T, Tables* R) {
@@ -349,11 +314,7 @@ int nkv_lookup_dev(nkv_ctx* c, const nkv_lookup_table* tables, int T, const void
     hipLaunchKernelGGL(k_lookup, dim3(blocks_for(q)), dim3(kBlock), 0, c->stream, R,
                        static_cast<const uint8_t*>(d_keys), d_koff, d_klen, q, d_hit, d_status, d_stage, err);
     HIPTRY(hipGetLastError());
-    if (d_err) return NKV_OK;
-    unsigned int h_err = 0;
-    HIPTRY(hipMemcpyAsync(&h_err, err, 4, hipMemcpyDeviceToHost, c->stream));
-    HIPTRY(hipStreamSynchronize(c->stream));
-    return h_err ? NKV_ERR_INVALID : NKV_OK;
+    return d_err ? NKV_OK : read_verdict(c, err);
 } NKV_CATCH
 
 int nkv_lookup_values_dev(nkv_ctx* c, const nkv_lookup_table* tables, int T, const uint64_t* d_hit,
@@ -374,9 +335,15 @@ int nkv_lookup_values_dev(nkv_ctx* c, const nkv_lookup_table* tables, int T, con
 
     // scratch in d_stmp, which carries nothing from call to call: the lengths
     // (q), their exclusive sums (q + 1) and the Values' addresses (q)
-    TRY(grow(c->d_stmp, 8 * (3 * q + 1)));
-    uint64_t* a = static_cast<uint64_t*>(c->d_stmp.p);
-    uint64_t *len = a, *off = a + q, *src = a + 2 * q + 1;
+    uint64_t *len, *off, *src;
+    const auto carve = [&](Carver k) {
+        len = k.take<uint64_t>(q);
+        off = k.take<uint64_t>(q + 1);
+        src = k.take<uint64_t>(q);
+        return k.bytes();
+    };
+    TRY(grow(c->d_stmp, carve(Carver())));
+    carve(Carver(c->d_stmp.p));
     size_t tb = 0;
     HIPTRY(scan_exclusive_u64(len, off, q, nullptr, &tb, c->stream));
     TRY(grow(c->d_tmp, tb));
@@ -392,7 +359,7 @@ int nkv_lookup_values_dev(nkv_ctx* c, const nkv_lookup_table* tables, int T, con
                        src, err);
     HIPTRY(hipGetLastError());
     HIPTRY(scan_exclusive_u64(len, off, q, c->d_tmp.p, &tb, c->stream));
-    hipLaunchKernelGGL(k_value_total, dim3(1), dim3(1), 0, c->stream, len, off, q, total);
+    hipLaunchKernelGGL(k_scan_total<uint64_t>, dim3(1), dim3(1), 0, c->stream, len, off, q, total);
     HIPTRY(hipGetLastError());
     // the verdict and the length, before anything is written
     uint64_t h[2] = {0, 0};

@@ -8,10 +8,10 @@
 // two entries compare equal, so the result does not depend on the algorithm.
 //
 // Stages, all on the context's stream:
-//   k_sort_validate  one lane per record: header bounds, the record ends where
-//                    the next starts; writes the dense entries (first 8 key
-//                    bytes big-endian zero-padded, KeySize, TotalSize).  The
-//                    host reads its error word before anything else is launched.
+//   k_sort_validate  one lane per record: its dense entry (record_dev.hpp
+//                    dense_entry: the record's span, it ends where the next
+//                    starts; the key's prefix, KeySize, TotalSize).  The host
+//                    reads its error word before anything else is launched.
 //   k_sort_tile      one workgroup sorts a tile of T = 1024 records in LDS as
 //                    (prefix u64, arrival index u32) pairs, 12 KiB, by a bitonic
 //                    network of 55 steps; a lane owns two compare-exchanges per
@@ -41,21 +41,18 @@
 //   scans            exclusive sums of the flags (output index) and the sizes
 //                    (output offset), then k_sort_scatter writes d_out_off /
 //                    d_out_src / source addresses and the totals.
-//   k_merge_copy     the merge's copy kernel (merge_copy_dev.hpp), unchanged.
+//   k_merge_copy     the copy kernel.  This tail is the merge's too
+//                    (merge_copy_dev.hpp write_table).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <vector>
-
-#include "bytes_dev.hpp"  // ld_le64, cmp_bytes
 #include "context.hpp"
-#include "merge_copy_dev.hpp"  // k_merge_copy, kCopyTile
+#include "merge_copy_dev.hpp"  // Slots, scatter_slots, write_table, kCopyTile
 
 using namespace nkv;
 
 namespace {
 
-constexpr int kHdr = 30;  // record.go:191-199: Crc 4 | Timestamp 8 | Status 1 | TypeInfo 1 | KeySize 8 | ValueSize 8
 constexpr uint32_t kTile = 1024;              // T: records one workgroup sorts in LDS
 constexpr uint32_t kSentinel = 0xFFFFFFFFu;   // arrival index of a slot past n (n <= 2^31 - 1)
 
@@ -63,10 +60,11 @@ struct Log {  // kernel argument: the write log
     const uint8_t* s;
     uint64_t len;
     const uint64_t* off;
+    // source word = arrival index
+    __device__ const uint8_t* record_at(uint64_t a) const { return s + off[a]; }
 };
 
-// Dense arrays over the log's records, by arrival index (Dense of merge.hip
-// without the timestamp).
+// Dense arrays over the log's records, by arrival index (record_dev.hpp DenseEntry).
 struct Dense {
     uint64_t* pfx;   // first 8 key bytes, big-endian, zero-padded
     uint64_t* klen;  // KeySize
@@ -77,36 +75,31 @@ __global__ __launch_bounds__(kBlock) void k_sort_validate(Log G, uint32_t n, Den
     const uint64_t gg = uint64_t(blockIdx.x) * kBlock + threadIdx.x;
     if (gg >= n) return;
     const uint32_t i = uint32_t(gg);
-    const uint64_t o = G.off[i];
-    bool bad = (i == 0 && o != 0) || !header_in(o, G.len);
-    if (!bad) {
-        const uint64_t ks = ld_le64(G.s + o + 14), vs = ld_le64(G.s + o + 22);
-        const uint64_t room = G.len - o - kHdr;
-        if (ks > room || vs > room - ks) {
-            bad = true;
-        } else {
-            const uint64_t end = o + kHdr + ks + vs;  // <= len: no overflow
-            const uint64_t next = i + 1 < n ? G.off[i + 1] : G.len;
-            if (end != next) bad = true;
-            const uint8_t* key = G.s + o + kHdr;
-            uint64_t p = 0;
-            for (uint32_t b = 0; b < 8 && b < ks; ++b) p |= uint64_t(key[b]) << (56 - 8 * b);
-            D.pfx[i] = p;
-            D.klen[i] = ks;
-            D.size[i] = kHdr + ks + vs;
-        }
+    DenseEntry e;
+    bool bad;
+    if (dense_entry(G.s, G.len, G.off, i, n, &e, &bad)) {
+        D.pfx[i] = e.pfx;
+        D.klen[i] = e.klen;
+        D.size[i] = e.size;
     }
     if (bad) atomicOr(err, 1u);
 }
 
+// The rest of the key of the validated record at arrival index a, for
+// cmp_prefixed: its length from the dense array, its tail in the log.
+struct Rest {
+    const Log& G;
+    const Dense& D;
+    uint32_t a;
+    __device__ uint64_t len() const { return D.klen[a]; }
+    __device__ const uint8_t* tail() const { return G.s + G.off[a] + kHdr + 8; }
+};
+
 // Keys of the validated records at arrival indices a and b, whose prefixes are
-// pa and pb: cmp_key of merge.hip.  The log is read only when both keys are
-// longer than 8 bytes and share their first 8.
+// pa and pb.  The log is read only when both keys are longer than 8 bytes and
+// share their first 8.
 __device__ inline int cmp_key(const Log& G, const Dense& D, uint64_t pa, uint32_t a, uint64_t pb, uint32_t b) {
-    if (pa != pb) return pa < pb ? -1 : 1;
-    const uint64_t la = D.klen[a], lb = D.klen[b];
-    if (la <= 8 || lb <= 8) return la < lb ? -1 : (la > lb ? 1 : 0);
-    return cmp_bytes(G.s + G.off[a] + kHdr + 8, la - 8, G.s + G.off[b] + kHdr + 8, lb - 8);
+    return cmp_prefixed(pa, Rest{G, D, a}, pb, Rest{G, D, b});
 }
 
 // The total order: key ascending, then arrival index ascending.
@@ -212,21 +205,8 @@ __global__ __launch_bounds__(kBlock) void k_sort_scatter(Log G, uint32_t n, cons
                                                          const uint64_t* __restrict__ osrc,
                                                          uint64_t* __restrict__ out_off, uint64_t* __restrict__ out_src,
                                                          uint64_t* __restrict__ src_addr, uint64_t* __restrict__ totals) {
-    const uint64_t s = uint64_t(blockIdx.x) * kBlock + threadIdx.x;
-    if (s >= n) return;
-    if (flag[s]) {
-        const uint64_t j = idx[s], a = osrc[s];
-        out_off[j] = ooff[s];
-        if (out_src) out_src[j] = a;
-        src_addr[j] = uint64_t(reinterpret_cast<uintptr_t>(G.s + G.off[a]));
-    }
-    if (s == n - 1) {
-        totals[0] = idx[s] + flag[s];
-        totals[1] = ooff[s] + osize[s];
-    }
+    scatter_slots(G, n, flag, idx, osize, ooff, osrc, out_off, out_src, src_addr, totals);
 }
-
-inline unsigned blocks_for(uint64_t n) { return unsigned((n + kBlock - 1) / kBlock); }
 
 }  // namespace
 
@@ -249,15 +229,21 @@ int nkv_sort_records_dev(nkv_ctx* c, const void* d_log, uint64_t log_len, const 
     // scratch in d_stmp (nothing in it outlives the call): nine u64 arrays of n,
     // then the two pair buffers (u64 prefixes, u32 arrival indices)
     const uint64_t n2 = (n + 1) & ~uint64_t(1);  // u32 arrays of n2 keep what follows 8-byte aligned
-    TRY(grow(c->d_stmp, 9 * 8 * n + 2 * (8 * n + 4 * n2)));
-    uint64_t* a = static_cast<uint64_t*>(c->d_stmp.p);
-    const Dense D{a, a + n, a + 2 * n};
-    uint64_t *flag = a + 3 * n, *osize = a + 4 * n, *osrc = a + 5 * n, *idx = a + 6 * n, *ooff = a + 7 * n,
-             *src_addr = a + 8 * n;
-    uint64_t* pfx[2] = {a + 9 * n, a + 10 * n};
-    uint32_t* arr[2] = {reinterpret_cast<uint32_t*>(a + 11 * n), reinterpret_cast<uint32_t*>(a + 11 * n) + n2};
+    Dense D;
+    Slots S;
+    uint64_t* pfx[2];
+    uint32_t* arr[2];
+    const auto carve = [&](Carver k) {
+        D = Dense{k.take<uint64_t>(n), k.take<uint64_t>(n), k.take<uint64_t>(n)};
+        S = take_slots(k, n);
+        for (auto& p : pfx) p = k.take<uint64_t>(n);
+        for (auto& p : arr) p = k.take<uint32_t>(n2);
+        return k.bytes();
+    };
+    TRY(grow(c->d_stmp, carve(Carver())));
+    carve(Carver(c->d_stmp.p));
     size_t tb = 0;
-    HIPTRY(scan_exclusive_u64(flag, idx, n, nullptr, &tb, c->stream));
+    HIPTRY(scan_exclusive_u64(S.flag, S.idx, n, nullptr, &tb, c->stream));
     TRY(grow(c->d_tmp, tb));
     TRY(grow(c->d_stats, 24));
     unsigned int* err = static_cast<unsigned int*>(c->d_stats.p);
@@ -269,10 +255,7 @@ int nkv_sort_records_dev(nkv_ctx* c, const void* d_log, uint64_t log_len, const 
     HIPTRY(hipMemsetAsync(err, 0, 24, c->stream));
     hipLaunchKernelGGL(k_sort_validate, dim3(blocks_for(n)), dim3(kBlock), 0, c->stream, G, n32, D, err);
     HIPTRY(hipGetLastError());
-    unsigned int h_err = 0;
-    HIPTRY(hipMemcpyAsync(&h_err, err, 4, hipMemcpyDeviceToHost, c->stream));
-    HIPTRY(hipStreamSynchronize(c->stream));
-    if (h_err) return NKV_ERR_INVALID;
+    TRY(read_verdict(c, err));
 
     // with NKV_TIMING_EVENTS: "leaf" = sort + survive + scans + scatter, "reduce" = the copy kernel
     TRY(mark(c, 0));
@@ -287,38 +270,18 @@ int nkv_sort_records_dev(nkv_ctx* c, const void* d_log, uint64_t log_len, const 
         cur ^= 1;
     }
     hipLaunchKernelGGL(k_sort_survive, dim3(blocks_for(n)), dim3(kBlock), 0, c->stream, G, n32, D, pfx[cur], arr[cur],
-                       flag, osize, osrc);
+                       S.flag, S.osize, S.osrc);
     HIPTRY(hipGetLastError());
-    HIPTRY(scan_exclusive_u64(flag, idx, n, c->d_tmp.p, &tb, c->stream));
-    HIPTRY(scan_exclusive_u64(osize, ooff, n, c->d_tmp.p, &tb, c->stream));
-    hipLaunchKernelGGL(k_sort_scatter, dim3(blocks_for(n)), dim3(kBlock), 0, c->stream, G, n32, flag, idx, osize, ooff,
-                       osrc, d_out_off, d_out_src, src_addr, totals);
-    HIPTRY(hipGetLastError());
-    TRY(mark(c, 1));
-    // out_len is known on the device only: the grid covers the bound (log_len),
-    // and tiles past out_len leave at once
-    hipLaunchKernelGGL(k_merge_copy, dim3(unsigned(tiles)), dim3(kBlock), 0, c->stream, static_cast<uint8_t*>(d_out),
-                       d_out_off, src_addr, totals);
-    HIPTRY(hipGetLastError());
-    TRY(mark(c, 2));
-    uint64_t h_tot[2] = {0, 0};
-    HIPTRY(hipMemcpyAsync(h_tot, totals, 16, hipMemcpyDeviceToHost, c->stream));
-    HIPTRY(hipStreamSynchronize(c->stream));
-    *n_out = h_tot[0];
-    *out_len = h_tot[1];
-    return NKV_OK;
+    return write_table(c, k_sort_scatter, G, n, S, c->d_tmp.p, tb, tiles, d_out, d_out_off, d_out_src, totals, n_out,
+                       out_len);
 } NKV_CATCH
 
 int nkv_sort_records(nkv_ctx* c, const uint8_t* log, uint64_t log_len, const uint64_t* rec_size, uint64_t n,
                      uint8_t* out, uint64_t out_cap, uint64_t* out_rec_size, uint64_t* n_out, uint64_t* out_len) try {
     TRY(bind(c));
     if (!n_out || !out_len || n > kMaxN || (n && (!log || !rec_size))) return NKV_ERR_INVALID;
-    uint64_t left = log_len;  // the sizes add up to the log exactly, term by term (no wrapped sum)
-    for (uint64_t i = 0; i < n; ++i) {
-        if (rec_size[i] > left) return NKV_ERR_INVALID;
-        left -= rec_size[i];
-    }
-    if (left != 0 || log_len > (uint64_t(1) << 62) || out_cap < log_len) return NKV_ERR_INVALID;
+    if (!records_fill(rec_size, n, log_len) || log_len > (uint64_t(1) << 62) || out_cap < log_len)
+        return NKV_ERR_INVALID;
     *n_out = 0;
     *out_len = 0;
     if (n == 0) return NKV_OK;
@@ -331,18 +294,11 @@ int nkv_sort_records(nkv_ctx* c, const uint8_t* log, uint64_t log_len, const uin
     uint64_t* d_size = static_cast<uint64_t*>(c->d_len.p);
     uint64_t* d_off = static_cast<uint64_t*>(c->d_off.p);
     uint64_t* d_out_off = static_cast<uint64_t*>(c->d_tmp2.p);
-    HIPTRY(hipMemcpyAsync(c->d_data.p, log, log_len, hipMemcpyHostToDevice, c->stream));
-    HIPTRY(hipMemcpyAsync(d_size, rec_size, 8 * n, hipMemcpyHostToDevice, c->stream));
-    TRY(nkv_record_offsets_dev(c, d_size, n, d_off));
+    TRY(upload_records(c, log, log_len, rec_size, n, c->d_data.p, d_size, d_off));
     TRY(nkv_sort_records_dev(c, c->d_data.p, log_len, d_off, n, c->d_nodes.p, log_len, d_out_off, nullptr, n_out,
                              out_len));
     if (*n_out == 0) return NKV_OK;
-    std::vector<uint64_t> off(*n_out);
-    HIPTRY(hipMemcpyAsync(out, c->d_nodes.p, *out_len, hipMemcpyDeviceToHost, c->stream));
-    HIPTRY(hipMemcpyAsync(off.data(), d_out_off, 8 * *n_out, hipMemcpyDeviceToHost, c->stream));
-    HIPTRY(hipStreamSynchronize(c->stream));
-    for (uint64_t j = 0; j < *n_out; ++j) out_rec_size[j] = (j + 1 < *n_out ? off[j + 1] : *out_len) - off[j];
-    return NKV_OK;
+    return download_table(c, c->d_nodes.p, *out_len, d_out_off, *n_out, out, out_rec_size);
 } NKV_CATCH
 
 }  // extern "C"

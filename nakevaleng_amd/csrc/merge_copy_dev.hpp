@@ -1,13 +1,15 @@
-// merge_copy_dev.hpp -- the record copy kernel shared by the compaction merge
-// (merge.hip) and the memtable flush (memtable.hip): both end with a list of
-// output offsets and source addresses and move the bytes the same way.  The
-// kernel has internal linkage, so each translation unit that includes this
-// header gets its own copy.
+// merge_copy_dev.hpp -- the tail shared by the compaction merge (merge.hip)
+// and the memtable flush (memtable.hip): both arrive at a flag, a size and a
+// source word per slot, and from there compact them, list output offsets and
+// source addresses and move the bytes the same way (write_table).  The kernels
+// have internal linkage, so each translation unit that includes this header
+// gets its own copy.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "bytes_dev.hpp"  // ld16_any
+#include "context.hpp"
 
 namespace nkv {
 namespace {
@@ -16,6 +18,44 @@ constexpr uint32_t kCopyTile = 16384;  // output bytes per workgroup
 constexpr uint32_t kCopyChunk = 16;    // output bytes per lane and step
 // records that can overlap one tile: at most kCopyTile / kHdr + 2 = 548
 constexpr uint32_t kCopyList = 640;
+static_assert(kCopyTile / kHdr + 2 <= kCopyList, "a tile's records fit the list");
+
+// Per-slot arrays of n entries each, carved in this order.
+struct Slots {
+    uint64_t* flag;      // 1: the slot holds a surviving record
+    uint64_t* osize;     // its TotalSize (0 where flag is 0)
+    uint64_t* osrc;      // its source word
+    uint64_t* idx;       // exclusive sum of flag: the output index
+    uint64_t* ooff;      // exclusive sum of osize: the output offset
+    uint64_t* src_addr;  // per output record: where its bytes lie
+};
+inline Slots take_slots(Carver& k, uint64_t n) {
+    return Slots{k.take<uint64_t>(n), k.take<uint64_t>(n), k.take<uint64_t>(n),
+                 k.take<uint64_t>(n), k.take<uint64_t>(n), k.take<uint64_t>(n)};
+}
+
+// One lane per slot: a surviving slot writes its output offset, its source
+// word (out_src nullable) and its record's address, which `in` makes of the
+// source word (in.record_at(w)); the last lane leaves totals = (n_out, out_len).
+template <class In>
+__device__ __forceinline__ void scatter_slots(const In& in, uint32_t n, const uint64_t* __restrict__ flag,
+                                              const uint64_t* __restrict__ idx, const uint64_t* __restrict__ osize,
+                                              const uint64_t* __restrict__ ooff, const uint64_t* __restrict__ osrc,
+                                              uint64_t* __restrict__ out_off, uint64_t* __restrict__ out_src,
+                                              uint64_t* __restrict__ src_addr, uint64_t* __restrict__ totals) {
+    const uint64_t s = uint64_t(blockIdx.x) * kBlock + threadIdx.x;
+    if (s >= n) return;
+    if (flag[s]) {
+        const uint64_t j = idx[s], w = osrc[s];
+        out_off[j] = ooff[s];
+        if (out_src) out_src[j] = w;
+        src_addr[j] = uint64_t(reinterpret_cast<uintptr_t>(in.record_at(w)));
+    }
+    if (s == n - 1) {
+        totals[0] = idx[s] + flag[s];
+        totals[1] = ooff[s] + osize[s];
+    }
+}
 
 // Output byte o of the merged table is byte o - off[j] of the record at
 // src[j], for the j with off[j] <= o < off[j + 1].  Chunks lie on the 16-byte
@@ -88,6 +128,35 @@ __global__ __launch_bounds__(kBlock) void k_merge_copy(uint8_t* __restrict__ out
             if (whole) *reinterpret_cast<uint4*>(out + ob) = make_uint4(w[0], w[1], w[2], w[3]);
         }
     }
+}
+
+// Behind the kernels that fill S.flag / S.osize / S.osrc: the two scans, the
+// caller's scatter kernel (its arguments after the input and n are the ones
+// given here), the copy over `tiles` tiles of d_out, and (n_out, out_len) read
+// back.  With NKV_TIMING_EVENTS "reduce" is the copy kernel.  tmp: the scan's
+// temporary of tb bytes.
+template <class Kernel, class In>
+int write_table(nkv_ctx* c, Kernel scatter, const In& in, uint64_t n, const Slots& S, void* tmp, size_t tb,
+                uint64_t tiles, void* d_out, uint64_t* d_out_off, uint64_t* d_out_src, uint64_t* totals,
+                uint64_t* n_out, uint64_t* out_len) {
+    HIPTRY(scan_exclusive_u64(S.flag, S.idx, n, tmp, &tb, c->stream));
+    HIPTRY(scan_exclusive_u64(S.osize, S.ooff, n, tmp, &tb, c->stream));
+    hipLaunchKernelGGL(scatter, dim3(blocks_for(n)), dim3(kBlock), 0, c->stream, in, uint32_t(n), S.flag, S.idx,
+                       S.osize, S.ooff, S.osrc, d_out_off, d_out_src, S.src_addr, totals);
+    HIPTRY(hipGetLastError());
+    TRY(mark(c, 1));
+    // out_len is known on the device only: the grid covers the bound (the
+    // bytes of the input), and tiles past out_len leave at once
+    hipLaunchKernelGGL(k_merge_copy, dim3(unsigned(tiles)), dim3(kBlock), 0, c->stream, static_cast<uint8_t*>(d_out),
+                       d_out_off, S.src_addr, totals);
+    HIPTRY(hipGetLastError());
+    TRY(mark(c, 2));
+    uint64_t h_tot[2] = {0, 0};
+    HIPTRY(hipMemcpyAsync(h_tot, totals, 16, hipMemcpyDeviceToHost, c->stream));
+    HIPTRY(hipStreamSynchronize(c->stream));
+    *n_out = h_tot[0];
+    *out_len = h_tot[1];
+    return NKV_OK;
 }
 
 }  // namespace
