@@ -18,11 +18,12 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
 SO = os.path.join(PKG, "libnkvmerkle.so")
-SOURCES = ["kernels.hip", "crc.hip", "bloom.hip", "merge.hip", "memtable.hip", "index.hip", "lookup.hip", "encode.hip",
+SOURCES = ["leaf.hip", "reduce.hip", "small_tree.hip", "plan.hip", "crc.hip", "bloom.hip", "merge.hip",
+           "memtable.hip", "index.hip", "lookup.hip", "encode.hip",
            "capi.cpp",
            "group.cpp", "host_stage.cpp"]
-HEADERS = ["internal.hpp", "context.hpp", "sha1_dev.hpp", "host_stage.hpp", "crc_dev.hpp", "murmur_dev.hpp",
-           "bytes_dev.hpp", "merge_copy_dev.hpp", "record_dev.hpp"]
+HEADERS = ["internal.hpp", "context.hpp", "sha1_dev.hpp", "sha1_feed_dev.hpp", "tree_dev.hpp", "host_stage.hpp",
+           "crc_dev.hpp", "murmur_dev.hpp", "bytes_dev.hpp", "merge_copy_dev.hpp", "record_dev.hpp"]
 ARCH = os.environ.get("NKV_OFFLOAD_ARCH", "gfx950")
 FLAGS = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-shared", "-pthread",
          "-Wall", "-Wno-unused-result"]

@@ -1,8 +1,9 @@
 // bytes_dev.hpp -- byte movers and searches of the record kernels (merge.hip,
 // memtable.hip, index.hip, lookup.hip, encode.hip and merge_copy_dev.hpp): 16
-// source bytes at any alignment out of aligned 16-byte loads, searches in an
-// ascending array by one lane and by a workgroup, and the scan's total.  The
-// record format itself and the key order are record_dev.hpp's.
+// source bytes at any alignment out of aligned 16-byte loads, a header's two
+// size fields out of aligned 8-byte loads, searches in an ascending array by
+// one lane and by a workgroup, and the scan's total.  The record format itself
+// and the key order are record_dev.hpp's.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -57,6 +58,26 @@ __device__ __forceinline__ uint4 ld_piece(uint64_t S, uint32_t cnt, uint32_t d) 
         if (d) v = funnel16(make_uint4(0, 0, 0, 0), v, 16 - d);
     }
     return v;
+}
+
+// KeySize and ValueSize (header bytes 14..29, record.go:191-199) of the
+// record at p, from two or three aligned 8-byte loads and a funnel shift
+// instead of sixteen byte loads (one line request per lane per load rather
+// than one per byte).  The third load is issued only when the fields are
+// not 8-byte aligned; it then holds byte 29, so every load stays inside an
+// aligned word that holds a header byte (no page can be crossed).  The header
+// reader of the leaf and locate kernels (leaf.hip, plan.hip).
+__device__ __forceinline__ void ld_header_sizes(const uint8_t* p, uint64_t& ks, uint64_t& vs) {
+    // pointer arithmetic on p (not an integer-to-pointer cast) keeps the global
+    // address space: global_load, not flat_load
+    const uint8_t* f = p + 14;
+    const uint32_t mis = uint32_t(reinterpret_cast<uintptr_t>(f) & 7u);
+    const uint64_t* q = reinterpret_cast<const uint64_t*>(f - mis);
+    const uint32_t sh = mis * 8u;
+    const uint64_t q0 = q[0], q1 = q[1];
+    const uint64_t q2 = sh ? q[2] : 0ull;
+    ks = sh ? (q0 >> sh) | (q1 << (64u - sh)) : q0;
+    vs = sh ? (q1 >> sh) | (q2 << (64u - sh)) : q1;
 }
 
 // The last index j in [lo, hi) with a[j] <= x; a ascending, a[lo] <= x.  The

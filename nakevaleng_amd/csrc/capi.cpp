@@ -2,7 +2,7 @@
 // the C-ABI declared in include/nkv_merkle.h.
 //
 // There is deliberately no CPU compute path here: every digest is produced by
-// the gfx950 kernels in kernels.hip.  A missing/unusable device is reported as
+// the gfx950 kernels in the *.hip units.  A missing/unusable device is reported as
 // NKV_ERR_DEVICE.
 #include <fcntl.h>
 #include <hip/hip_runtime.h>

@@ -1,6 +1,6 @@
 // crc_dev.hpp -- CRC-32/IEEE (Go hash/crc32 ChecksumIEEE: reflected, poly
 // 0xEDB88320, init and final XOR 0xFFFFFFFF) building blocks shared by the
-// checksum kernels (crc.hip) and the leaf kernel's verify form (kernels.hip).
+// checksum kernels (crc.hip) and the leaf kernel's verify form (leaf.hip).
 // Slicing-by-4: one 32-bit little-endian word per step, four lookups into
 // 256-entry tables that the kernels stage in LDS.
 #pragma once

@@ -74,6 +74,11 @@ hipError_t launch_leaf_offsets(const uint8_t* base, const uint64_t* off, const u
 // = longest chain (compressions - 1) of a group the non-priority waves take
 // when the longest chain bounds the batch.
 uint64_t queue_words(uint64_t n);
+// q: [0] front ticket, [1] back ticket, [2] first short group, [3] unused,
+//    [4..5] the batch's work (u64), [6..7] pad; then kSimdKeys per-SIMD
+//    arrivals, then the groups' claim flags (k_leaf_queue).
+constexpr uint32_t kSimdKeys = 8 * 8 * 2 * 16 * 4;  // xcc, se, sh, cu, simd
+constexpr uint32_t kQueueHeader = 8;  // tickets, first short group, pad, work (u64), pad
 struct QueueInit {
     uint32_t* q = nullptr;  // nullptr: no queue follows the sort
     uint64_t nq = 0;
@@ -96,6 +101,9 @@ uint64_t locate_part_words(uint64_t n);
 hipError_t launch_locate(const uint8_t* stream, uint64_t stream_len, const uint64_t* rec_off,
                          uint64_t n, uint64_t* voff, uint64_t* vlen, unsigned int* err, unsigned int* range,
                          uint32_t* part, hipStream_t s);
+// The fold alone (k_locate_fold over nb workgroups' triples), for the leaf
+// passes that leave their own partials (leaf.hip); only launches.
+void launch_locate_fold(const uint32_t* part, uint32_t nb, unsigned int* err, unsigned int* range, hipStream_t s);
 // The records form's leaf pass (k_leaf_records): locate each record's value and
 // hash it in input order (policy 0), only in waves of narrow block counts (1,
 // the rest deferred to the length-sorted pass), or never (2); voff / vlen
@@ -130,7 +138,7 @@ hipError_t launch_crc_spans(const uint8_t* base, const uint64_t* off, const uint
 hipError_t launch_record_crc(const uint8_t* stream, uint64_t stream_len, const uint64_t* rec_off, uint64_t n,
                              uint32_t* out, unsigned long long* stats, int variant, hipStream_t s,
                              Gate gate = Gate{}, bool init_stats = true);
-// The compaction read in one pass (kernels.hip k_leaf_verify): for the record at
+// The compaction read in one pass (leaf.hip k_leaf_verify): for the record at
 // stream + rec_off[i], its CRC of Key ++ Value into crc_out[i] (nullable),
 // checked against the stored Crc into stats as launch_record_crc does (stats
 // initialised by the caller), and the leaf digest of its Value into nodes
@@ -163,7 +171,7 @@ hipError_t launch_bloom_staged(int mode, const uint8_t* base, const uint64_t* of
                                uint64_t stream_len, uint64_t n, uint32_t m, uint32_t k, uint32_t seed0,
                                uint32_t* bits, unsigned int* err, uint32_t* scratch, hipStream_t s);
 hipError_t launch_fill(uint8_t* buf, uint64_t nbytes, uint64_t seed, hipStream_t s);
-// One-launch small tree (kernels.hip k_small_tree): desc = n (offset, length)
+// One-launch small tree (small_tree.hip k_small_tree): desc = n (offset, length)
 // u64 pairs, value i at vals + offset (16-byte aligned); out receives
 // the nodes (level-major) and, at out + img_at (16-byte aligned; 0 = none), the Serialize
 // image.  scratch: 20 n device bytes; ticket: one device u32, zero before the
@@ -175,7 +183,7 @@ constexpr uint32_t kSmallSeg = 16384;  // LDS stage: the staged input, then imag
 hipError_t launch_small_tree(const uint64_t* desc, const uint8_t* vals, uint32_t vbytes, uint32_t n, uint8_t* out,
                              uint32_t img_at, uint8_t* scratch, unsigned int* ticket, unsigned int* done, uint32_t seq,
                              hipStream_t s);
-// The resident small-tree service (kernels.hip k_small_service,
+// The resident small-tree service (small_tree.hip k_small_service,
 // NKV_OPT_SMALL_PATH 3).  The host writes a request (the fields after `done`,
 // as launch_small_tree's arguments) and then its seq into `doorbell`; the
 // service answers with seq in `done` behind every output byte.  Two copies of
@@ -231,5 +239,26 @@ hipError_t set_clock_probe(unsigned long long* p, hipStream_t s);
 // ticket: one device u32, zero before the first launch (each launch leaves it zero)
 hipError_t launch_len_range(const uint64_t* len, uint64_t n, unsigned int* out, uint32_t* part, unsigned int* ticket,
                             hipStream_t s);
+
+#ifdef NKV_DIAG
+// Diagnostic build only (tools/diag_timeline.py): per-wave s_memtime /
+// s_memrealtime stamps, never part of an output.  A unit that stamps
+// (leaf.hip, small_tree.hip) defines its own g_diag; nkv_diag_set_buffer sets
+// both.
+hipError_t set_diag_leaf(unsigned long long* p);
+hipError_t set_diag_small(unsigned long long* p);
+#define NKV_STAMP(slot)                                                                 \
+    do {                                                                                \
+        if (g_diag && (threadIdx.x & 63) == 0) {                                        \
+            const size_t w_ = size_t(blockIdx.x) * (kBlock / 64) + (threadIdx.x >> 6);   \
+            g_diag[w_ * 8 + 2 * (slot)] = __builtin_amdgcn_s_memrealtime();             \
+            g_diag[w_ * 8 + 2 * (slot) + 1] = __builtin_amdgcn_s_memtime();             \
+        }                                                                               \
+    } while (0)
+#else
+#define NKV_STAMP(slot) \
+    do {                \
+    } while (0)
+#endif
 
 }  // namespace nkv

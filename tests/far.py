@@ -3,7 +3,7 @@ numpy, no torch), shared by tests/test_gpu_far.py and tests/test_far_layout.py.
 
 The leaf kernels address a wave's 64 values as 32-bit offsets from a
 wave-uniform base where they can and take 64-bit addresses when the values lie
-too far apart (the guards quoted at *_flip below, csrc/kernels.hip).  A case
+too far apart (the guards quoted at *_flip below, csrc/sha1_feed_dev.hpp).  A case
 here is a COMPACT layout -- one small contiguous host array, what the oracle
 hashes and what the near twin uploads -- plus ISLANDS that map ranges of it to
 places gigabytes apart inside one big device allocation of ALLOC bytes.

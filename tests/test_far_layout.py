@@ -1,7 +1,7 @@
 """CPU: the far layouts of tests/far.py are what tests/test_gpu_far.py takes
 them for -- far where they say far, on the intended side of the intended guard
 where they say threshold, inside the allocation, and free of overlaps.  The
-guards are evaluated here as csrc/kernels.hip writes them, over the placed
+guards are evaluated here as csrc/sha1_feed_dev.hpp writes them, over the placed
 addresses, independently of the flip distances far.py derives."""
 import numpy as np
 import pytest

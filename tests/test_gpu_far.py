@@ -2,8 +2,8 @@
 
 The leaf kernels address a wave's 64 values as 32-bit offsets from a
 wave-uniform base and fall back to 64-bit addresses when the values lie too
-far apart (csrc/kernels.hip: ring_vc_blocks, sha1_blocks_pair,
-sha1_blocks_shift, k_leaf's fallthroughs).  Here one allocation of 9 GiB is
+far apart (csrc/sha1_feed_dev.hpp: ring_vc_blocks, sha1_blocks_pair,
+sha1_blocks_shift; csrc/leaf.hip: k_leaf's fallthroughs).  Here one allocation of 9 GiB is
 never filled as a whole: each case uploads a few MiB into islands at 0, about
 2^32 and about 2 * 2^32 (tests/far.py) and asserts that
   1. the device result equals the oracle's over the compact host array,

@@ -5,10 +5,11 @@
 // L2 mode: every wave reads the same 64 values (4 MiB at 1,024 blocks);
 // HBM mode: each wave its own.
 //   hipcc --offload-arch=gfx950 -O3 -I nakevaleng_amd/csrc tools/lone_wave.hip -o tools/lone_wave.bin
-#include "../nakevaleng_amd/csrc/kernels.hip"
+#include "../nakevaleng_amd/csrc/sha1_feed_dev.hpp"
 
 #include <stdio.h>
 #include <stdlib.h>
+#include <algorithm>
 #include <vector>
 
 namespace nkv {

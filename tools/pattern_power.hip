@@ -12,13 +12,26 @@
 // Prints ms per launch, the in-kernel clock of the last launch and cycles per
 // block.
 //   hipcc --offload-arch=gfx950 -O3 -I nakevaleng_amd/csrc tools/pattern_power.hip -o tools/pattern_power.bin
-#include "../nakevaleng_amd/csrc/kernels.hip"
+#include "../nakevaleng_amd/csrc/internal.hpp"
+#include "../nakevaleng_amd/csrc/sha1_feed_dev.hpp"
+#include "../nakevaleng_amd/csrc/tree_dev.hpp"
 
 #include <stdio.h>
 #include <unistd.h>
 #include <vector>
 
 namespace nkv {
+
+// the library's synthetic bytes (plan.hip k_fill): word k = splitmix64(seed, k), little endian
+__global__ void k_fill_words(uint64_t* __restrict__ buf, uint64_t words, uint64_t seed) {
+    const uint64_t stride = uint64_t(gridDim.x) * blockDim.x;
+    for (uint64_t k = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x; k < words; k += stride) {
+        uint64_t z = seed + (k + 1) * 0x9E3779B97F4A7C15ull;
+        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+        z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+        buf[k] = z ^ (z >> 31);
+    }
+}
 
 template <int P>
 __global__ __launch_bounds__(kBlock, kLeafWavesPerSimd) void k_pat(const uint8_t* __restrict__ base, uint32_t nblk,
@@ -126,7 +139,8 @@ int main() {
     (void)hipMemset(d, 0x5a, bytes);
     printf("constant bytes (0x5a):\n");
     ramp(d, nodes, clk, grid, 400, 0);
-    hipLaunchKernelGGL(k_fill, dim3(4096), dim3(kBlock), 0, 0, d, bytes, 0x6e616b65ull);
+    hipLaunchKernelGGL(k_fill_words, dim3(4096), dim3(kBlock), 0, 0, reinterpret_cast<uint64_t*>(d), bytes / 8,
+                       0x6e616b65ull);
     printf("splitmix64 bytes:\n");
     ramp(d, nodes, clk, grid, 400, 0);
     ramp(d, nodes, clk, grid, 400, 1000);
