@@ -41,6 +41,11 @@
  *     skiplist.Write        core/skiplist/skiplist.go:62-120    nkv_sort_records
  *   record.New / ToBytes    core/record/record.go:49-60,175-187 nkv_encode_records_dev /
  *   wal.flushPartialBufferToSegment  core/wal/wal.go:199-232    nkv_encode_records
+ *   (*HLL).Add / Estimate   ds/hll/hll.go:43-62, 75-92          nkv_hll_add[_records][_dev] /
+ *                                                               nkv_hll_estimate
+ *   cmsketch.New sizing     ds/cmsketch/cmsketch.go:18-24       nkv_cms_params
+ *   (*CountMinSketch).Insert / Query  cmsketch.go:76-111        nkv_cms_insert[_records][_dev] /
+ *                                                               nkv_cms_query[_dev]
  *
  * Conventions
  *   - Every function returns an nkv_status (0 = NKV_OK) unless noted; nothing
@@ -72,7 +77,8 @@
  *         the group calls), 4-byte aligned: level starts inside a nodes buffer
  *         are multiples of 20 bytes, no more;
  *       uint32_t arrays and filter words (d_crc, the encode's d_crc included,
- *         d_err, d_bits), 4-byte aligned;
+ *         d_err, d_bits, the sketches' d_reg and d_table, nkv_cms_query_dev's
+ *         d_out), 4-byte aligned;
  *       uint64_t arrays (d_rec_off, d_voff, d_vlen, d_stats, d_out_off, the
  *         encode's d_out_off included, d_out_src, d_hit), 8-byte aligned.
  *     nkv_leaf_hash*_dev write level 0 only (20 n bytes); nkv_tree_reduce_dev
@@ -82,9 +88,12 @@
  *     d_hit and d_status and q T bytes of d_stage; nkv_lookup_values_dev
  *     writes *out_len bytes and q + 1 entries of d_out_off;
  *     nkv_encode_records_dev writes *out_len bytes and n entries of d_out_off
- *     and of d_crc.  Inputs are never
+ *     and of d_crc; d_reg is 2^p bytes and d_table 4 K M bytes, both updated
+ *     in place and never touched outside those extents; nkv_cms_query_dev
+ *     writes n entries of d_out.  Inputs are never
  *     written: values, record streams, offset and length arrays, the merge's
- *     runs, the sort's log, and the lookup's tables, filters and query keys are read in place
+ *     runs, the sort's log, the lookup's tables, filters and query keys, and the
+ *     sketches' keys and the queried d_table are read in place
  *     (at any alignment where they are bytes).
  *   - Offsets, strides and stream lengths are full 64-bit quantities: the
  *     values, spans or records of one call may lie any distance apart inside
@@ -230,6 +239,14 @@ int nkv_ctx_sync(nkv_ctx *ctx);
                                       memory; else as 1); 1 = in host-coherent memory.  Answers
                                       always land in host memory.  A change stops a running
                                       service; the next call starts it in the new form */
+#define NKV_OPT_SKETCH_PATH 21 /* HLL adds and CMS inserts: 0 (default) = auto (by n and the table
+                                  size); 1 = one lane per key straight onto
+                                  the caller's buffer (a compare-and-swap on the register's dword
+                                  only when the value rises, one atomicAdd per counter); 2 = a
+                                  persistent grid whose workgroups keep private copies in LDS and
+                                  merge them once at the end (a CMS table of more than 16384
+                                  counters does not fit and takes 1).  Every value gives the same
+                                  bytes */
 int nkv_ctx_set_option(nkv_ctx *ctx, int key, int64_t value);
 /* Which path the latest host-buffer tree call of the context took */
 #define NKV_PATH_GRID 0  /* copies + leaf kernel + per-level reduce launches */
@@ -601,6 +618,89 @@ int nkv_encode_records_dev(nkv_ctx *ctx, const nkv_puts *puts, void *d_out, uint
  * NULL it is a size query.  Synchronous. */
 int nkv_encode_records(nkv_ctx *ctx, const nkv_puts *puts, uint8_t *out, uint64_t out_cap,
                        uint64_t *out_rec_size, uint32_t *crc_out, uint64_t *out_len);
+
+/* ---- sketches: HyperLogLog (ds/hll) and Count-Min Sketch (ds/cmsketch) ----
+ * The only typed values the reference's engine knows (WrapperEngine.PutHLL /
+ * PutCMS, engine/wrappereng/wrappereng.go:57-83).  Both hash every key with
+ * MurmurHash3_x86_32 (spaolacci/murmur3 Sum32), as the filter does.
+ *
+ * HLL, precision p in [NKV_HLL_MIN_PRECISION, NKV_HLL_MAX_PRECISION], 2^p
+ * registers of one byte.  Add(key) (hll.go:43-62): h = murmur3(key, seed 0),
+ * Reg[h >> (32 - p)] = max(itself, 1 + TrailingZeros32(h)), which is 33 for
+ * h == 0 (the empty key: it sets Reg[0] = 33).
+ *
+ * CMS, K rows of M uint32_t counters.  Row i hashes with seed seed0 + i
+ * (cmsketch.go:28-38; the reference draws seed0 from the clock, here it is an
+ * argument, modulo 2^32).  Insert (:76-87) adds 1 to Contents[i][murmur3(key,
+ * seed0 + i) % M] in every row, in uint32_t arithmetic: a counter wraps at
+ * 2^32.  Query (:91-111) is the minimum of those K counters.
+ *
+ * Deviations from the reference: cmsketch.New accepts epsilon = 0, delta = 0
+ * and delta = 1 (+Inf conversions, K = 0); nkv_cms_params returns
+ * NKV_ERR_INVALID unless 0 < epsilon <= 1, 0 < delta < 1 and M <= 2^32 - 1, and
+ * the insert and query entries need M >= 1, K >= 1 and K M <= 2^31 - 1.  The gob
+ * encodings (EncodeToBytes / DecodeFromBytes) are not covered.
+ *
+ * Argument rules, as for the filter entries: NKV_ERR_INVALID for a null
+ * context, p outside [4, 16], m = 0, k = 0, K M too large, a null output (or
+ * null d_table of the query), n > 2^31 - 1; then n = 0 returns NKV_OK and
+ * touches nothing; then a null input is NKV_ERR_INVALID.  Max and wrapping add
+ * commute: the result does not depend on NKV_OPT_SKETCH_PATH, on the grid or on
+ * how the keys are split over calls. */
+#define NKV_HLL_MIN_PRECISION 4
+#define NKV_HLL_MAX_PRECISION 16
+#define NKV_HLL_ESTIMATE_REFERENCE 0 /* hll.go:75-92, literal */
+#define NKV_HLL_ESTIMATE_STANDARD 1  /* sum of 2^-Reg, same alpha and corrections */
+
+/* Device forms, asynchronous on the context's stream.  Keys as for
+ * nkv_bloom_insert_dev (d_keys + d_off[i], d_len[i], any alignment) or the keys
+ * of the records at d_stream + d_rec_off[i]; the records forms return
+ * NKV_ERR_INVALID (after a sync) if a header or key reaches outside the stream
+ * (that record contributes nothing).  d_reg: 2^p bytes, 4-byte aligned, max-ed
+ * in place, so several calls build one HLL.  d_table: k rows of m uint32_t, row
+ * i at d_table + i * m, 4-byte aligned, added to in place. */
+int nkv_hll_add_dev(nkv_ctx *ctx, const void *d_keys, const uint64_t *d_off, const uint64_t *d_len,
+                    uint64_t n, int p, void *d_reg);
+int nkv_hll_add_records_dev(nkv_ctx *ctx, const void *d_stream, uint64_t stream_len,
+                            const uint64_t *d_rec_off, uint64_t n, int p, void *d_reg);
+int nkv_cms_insert_dev(nkv_ctx *ctx, const void *d_keys, const uint64_t *d_off, const uint64_t *d_len,
+                       uint64_t n, uint32_t m, uint32_t k, uint32_t seed0, uint32_t *d_table);
+int nkv_cms_insert_records_dev(nkv_ctx *ctx, const void *d_stream, uint64_t stream_len,
+                               const uint64_t *d_rec_off, uint64_t n, uint32_t m, uint32_t k,
+                               uint32_t seed0, uint32_t *d_table);
+/* d_out[i] = the minimum over the k rows */
+int nkv_cms_query_dev(nkv_ctx *ctx, const void *d_keys, const uint64_t *d_off, const uint64_t *d_len,
+                      uint64_t n, uint32_t m, uint32_t k, uint32_t seed0, const uint32_t *d_table,
+                      uint32_t *d_out);
+
+/* Host-pointer forms, synchronous, staged like nkv_bloom_build /
+ * nkv_bloom_from_records (stream and rec_size as for nkv_tree_from_records);
+ * reg (2^p bytes) and table (k m counters) are read, updated and written back. */
+int nkv_hll_add(nkv_ctx *ctx, const uint8_t *keys, const uint64_t *off, const uint64_t *len,
+                uint64_t n, int p, uint8_t *reg);
+int nkv_hll_add_records(nkv_ctx *ctx, const uint8_t *stream, uint64_t stream_len,
+                        const uint64_t *rec_size, uint64_t n, int p, uint8_t *reg);
+int nkv_cms_insert(nkv_ctx *ctx, const uint8_t *keys, const uint64_t *off, const uint64_t *len,
+                   uint64_t n, uint32_t m, uint32_t k, uint32_t seed0, uint32_t *table);
+int nkv_cms_insert_records(nkv_ctx *ctx, const uint8_t *stream, uint64_t stream_len,
+                           const uint64_t *rec_size, uint64_t n, uint32_t m, uint32_t k,
+                           uint32_t seed0, uint32_t *table);
+int nkv_cms_query(nkv_ctx *ctx, const uint8_t *keys, const uint64_t *off, const uint64_t *len,
+                  uint64_t n, uint32_t m, uint32_t k, uint32_t seed0, const uint32_t *table,
+                  uint32_t *out);
+
+/* Pure host functions, no context.  nkv_cms_params: M = ceil(e / epsilon),
+ * K = ceil(ln(1 / delta)) (cmsketch.go:18-24).  nkv_hll_estimate over 2^p
+ * registers: mode NKV_HLL_ESTIMATE_REFERENCE is (*HLL).Estimate taken literally
+ * -- its sum adds math.Pow(float64(-val), 2) with val a uint8, so -val wraps
+ * and the term is (256 - val)^2 (0 for an empty register), not 2^-val; alpha =
+ * 0.7213 / (1 + 1.079 / M); estimation = alpha M^2 / sum; below 2.5 M with
+ * empty registers it is M ln(M / empty), above 2^32 / 30 it is -2^32 ln(1 -
+ * estimation / 2^32).  In effect: linear counting while empty registers
+ * remain, a meaningless small number after that, NaN for an empty HLL.  Mode
+ * NKV_HLL_ESTIMATE_STANDARD sums 2^-val instead, the rest unchanged. */
+int nkv_cms_params(double epsilon, double delta, uint32_t *m, uint32_t *k);
+int nkv_hll_estimate(const uint8_t *reg, int p, int mode, double *out);
 
 /* ---- Index and Summary tables (core/sstable/sstable.go:76-139) ----
  * makeIndexAndSummary over a Data table: for records i = 0..n-1 with key K_i

@@ -38,6 +38,11 @@ NKV_OPT_ARENA_COHERENT = 17
 NKV_OPT_SIDE_GATE = 18
 NKV_OPT_QUEUE_PAIR = 19  # retired: accepts only 0
 NKV_OPT_SERVICE_MAILBOX = 20
+NKV_OPT_SKETCH_PATH = 21  # 0 auto, 1 direct global atomics, 2 workgroup-private copies in LDS
+NKV_HLL_MIN_PRECISION = 4
+NKV_HLL_MAX_PRECISION = 16
+NKV_HLL_ESTIMATE_REFERENCE = 0
+NKV_HLL_ESTIMATE_STANDARD = 1
 NKV_PATH_GRID = 0
 NKV_PATH_SMALL = 1
 NKV_OPT_DEEP_PREFETCH = 3  # retired: accepts only 3
@@ -60,6 +65,7 @@ _u64p = ctypes.POINTER(ctypes.c_uint64)
 _vp = ctypes.c_void_p
 _u64 = ctypes.c_uint64
 _int = ctypes.c_int
+_u32 = ctypes.c_uint32
 
 class NkvTable(ctypes.Structure):
     """struct nkv_table (include/nkv_merkle.h): one table of device-resident leaves."""
@@ -174,6 +180,18 @@ SIGNATURES = {
     "nkv_sort_records": (_int, [_vp, _vp, _u64, _vp, _u64, _vp, _u64, _vp, _u64p, _u64p]),
     "nkv_encode_records_dev": (_int, [_vp, ctypes.POINTER(NkvPuts), _vp, _u64, _vp, _vp, _u64p]),
     "nkv_encode_records": (_int, [_vp, ctypes.POINTER(NkvPuts), _vp, _u64, _vp, _vp, _u64p]),
+    "nkv_hll_add_dev": (_int, [_vp, _vp, _vp, _vp, _u64, _int, _vp]),
+    "nkv_hll_add_records_dev": (_int, [_vp, _vp, _u64, _vp, _u64, _int, _vp]),
+    "nkv_cms_insert_dev": (_int, [_vp, _vp, _vp, _vp, _u64, _u32, _u32, _u32, _vp]),
+    "nkv_cms_insert_records_dev": (_int, [_vp, _vp, _u64, _vp, _u64, _u32, _u32, _u32, _vp]),
+    "nkv_cms_query_dev": (_int, [_vp, _vp, _vp, _vp, _u64, _u32, _u32, _u32, _vp, _vp]),
+    "nkv_hll_add": (_int, [_vp, _vp, _vp, _vp, _u64, _int, _vp]),
+    "nkv_hll_add_records": (_int, [_vp, _vp, _u64, _vp, _u64, _int, _vp]),
+    "nkv_cms_insert": (_int, [_vp, _vp, _vp, _vp, _u64, _u32, _u32, _u32, _vp]),
+    "nkv_cms_insert_records": (_int, [_vp, _vp, _u64, _vp, _u64, _u32, _u32, _u32, _vp]),
+    "nkv_cms_query": (_int, [_vp, _vp, _vp, _vp, _u64, _u32, _u32, _u32, _vp, _vp]),
+    "nkv_cms_params": (_int, [ctypes.c_double, ctypes.c_double, ctypes.POINTER(_u32), ctypes.POINTER(_u32)]),
+    "nkv_hll_estimate": (_int, [_vp, _int, _int, ctypes.POINTER(ctypes.c_double)]),
     "nkv_summary_entries": (_u64, [_u64, _u64]),
     "nkv_index_summary_dev": (_int, [_vp, _vp, _u64, _vp, _u64, _u64, _vp, _u64, _vp, _u64, _u64p, _u64p]),
     "nkv_index_summary_from_records": (_int, [_vp, _vp, _u64, _vp, _u64, _u64, _vp, _u64, _vp, _u64, _u64p,

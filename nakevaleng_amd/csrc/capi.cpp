@@ -984,6 +984,10 @@ int nkv_ctx_set_option(nkv_ctx* c, int key, int64_t value) try {
             if (value < 0 || value > 2) return NKV_ERR_INVALID;
             c->bloom_path = int(value);
             return NKV_OK;
+        case NKV_OPT_SKETCH_PATH:
+            if (value < 0 || value > 2) return NKV_ERR_INVALID;
+            c->sketch_path = int(value);
+            return NKV_OK;
         case NKV_OPT_HOST_THREADS:
             if (value < 0 || value > 256) return NKV_ERR_INVALID;
             c->stage.want_threads = int(value);

@@ -161,6 +161,7 @@ struct nkv_ctx {
     int queue_split = 32;   // NKV_OPT_QUEUE_SPLIT
     int queue_waves = 3;    // NKV_OPT_QUEUE_WAVES
     int bloom_path = 2;     // NKV_OPT_BLOOM_PATH
+    int sketch_path = 0;    // NKV_OPT_SKETCH_PATH
     int crc_load = 0;       // NKV_OPT_CRC_LOAD
     int records_fused = 1;  // NKV_OPT_RECORDS_FUSED
     int table_lanes = 2;    // NKV_OPT_TABLE_LANES
@@ -282,6 +283,9 @@ int upload_records(nkv_ctx* c, const uint8_t* stream, uint64_t stream_len, const
 // its bytes to out, and its offsets d_off as sizes to out_rec_size.
 int download_table(nkv_ctx* c, const void* d_table, uint64_t len, const uint64_t* d_off, uint64_t n, uint8_t* out,
                    uint64_t* out_rec_size);
+// Contiguous host bytes -> d (bulk path) plus n u64 -> d64 (through h_stage).
+int stage_stream(nkv_ctx* c, const uint8_t* src, uint64_t bytes, DevBuf& d, const uint64_t* v64, uint64_t n,
+                 DevBuf& d64);
 // Events bracketing a host-buffer call (which = 0 before the upload, 1 after the download).
 int host_mark(nkv_ctx* c, int which);
 

@@ -571,3 +571,48 @@ def get_many(tables: Sequence[ResidentTable], keys: Sequence[bytes], device=None
         return values
     return (values, d_stage.cpu().numpy()[:q * T].reshape(q, T).copy(),
             d_hit.cpu().numpy().view(np.uint64)[:q].copy())
+
+
+# ---------------------------------------------------------------------------
+# sketches over a table's keys (nkv_hll_add_records_dev / nkv_cms_insert_records_dev)
+
+def key_sketches(table, precision: Optional[int] = None, cms=None, seed: Optional[int] = None, device=None):
+    """An HLL and / or a Count-Min Sketch over the keys of one Data table:
+    (sketch.HLL or None, sketch.CountMinSketch or None).  `table` is a Table
+    (stream, RecSize array), uploaded once with upload_table, or a
+    ResidentTable, whose resident stream and offsets are used as they are, with
+    no upload.  `precision` asks for the HLL -- its EstimateStandard() says how
+    many distinct keys a flush of this log will keep, the expected_elements of
+    the flushed table's filter -- and `cms` = (epsilon, delta) for the Count-Min
+    Sketch (writes per key), seeded with `seed` as sketch.NewCMS takes it."""
+    import torch
+    from . import _lib, sketch
+    if not isinstance(table, ResidentTable):
+        table = upload_table(table, device=device)
+    dev_index = rank_device(device if device is not None else table.device)
+    if table.device != dev_index:
+        raise ValueError(f"key_sketches: the table is resident on device {table.device}, not {dev_index}")
+    ctx = _lib.default_context(dev_index)
+    L = _lib.lib()
+    dev = torch.device("cuda", dev_index)
+    hll = sketch.New(precision, ctx=ctx) if precision is not None else None
+    cm = sketch.NewCMS(cms[0], cms[1], seed=seed, ctx=ctx) if cms is not None else None
+    stream = torch.cuda.current_stream(dev)
+    d_reg = d_tab = None
+    with ctx.on_stream(stream.cuda_stream):
+        if hll is not None:
+            d_reg = torch.zeros(hll.M, dtype=torch.uint8, device=dev)
+            _lib.check(L.nkv_hll_add_records_dev(ctx.h, table.stream.data_ptr(), table.nbytes,
+                                                 table.rec_off.data_ptr(), table.n, hll.P, d_reg.data_ptr()),
+                       "key sketches: HLL")
+        if cm is not None:
+            d_tab = torch.zeros(4 * cm.M * cm.K, dtype=torch.uint8, device=dev)
+            _lib.check(L.nkv_cms_insert_records_dev(ctx.h, table.stream.data_ptr(), table.nbytes,
+                                                    table.rec_off.data_ptr(), table.n, cm.M, cm.K, cm.HashSeeds[0],
+                                                    d_tab.data_ptr()), "key sketches: CMS")
+        stream.synchronize()
+    if hll is not None:
+        hll._reg = d_reg.cpu().numpy().copy()
+    if cm is not None:
+        cm._table = d_tab.cpu().numpy().view(np.uint32).reshape(cm.K, cm.M).copy()
+    return hll, cm

@@ -6,6 +6,8 @@
                              serialized Data table
   make_filter_contents       the bits of sstable.makeFilter  sstable.go:49-56 (8f row 4)
   make_filter_from_records   the same over the keys of a serialized Data table
+  key_sketches_from_records  an HLL and / or a Count-Min Sketch over the same keys
+                             (ds/hll, ds/cmsketch; nakevaleng_amd/sketch.py)
   index_and_summary          the bytes of sstable.makeIndexAndSummary  sstable.go:76-139
   make_index_and_summary_from_records   the same into the two files
   make_table_secondaries_from_records   MakeTableSecondaries over a serialized
@@ -107,6 +109,33 @@ def make_filter_from_records(stream, rec_sizes, seed: int, false_positive_rate: 
                                                  _lib.p8(bits)))
     bf._contents = bytearray(bits.tobytes())
     return bf
+
+
+def key_sketches_from_records(stream, rec_sizes, precision: Optional[int] = None, cms=None,
+                              seed: Optional[int] = None, ctx=None):
+    """The sketches of a serialized Data table's keys, hashed in place on the
+    device: (HLL or None, CountMinSketch or None).  `precision` asks for an HLL
+    (sketch.New(precision) with every key Added: its EstimateStandard() is the
+    number of distinct keys, the expected_elements of the table's filter);
+    `cms` = (epsilon, delta) asks for a Count-Min Sketch (sketch.NewCMS(epsilon,
+    delta, seed) with every key Inserted: writes per key)."""
+    from . import sketch
+    sizes = np.ascontiguousarray(rec_sizes, dtype=np.uint64)
+    buf = np.frombuffer(bytes(stream), np.uint8) if not isinstance(stream, np.ndarray) else stream
+    buf = np.ascontiguousarray(buf, dtype=np.uint8)
+    p_buf = (buf if buf.size else np.zeros(1, np.uint8)).ctypes.data
+    p_sizes = (sizes if sizes.size else np.zeros(1, np.uint64)).ctypes.data
+    hll = sketch.New(precision, ctx=ctx) if precision is not None else None
+    cm = sketch.NewCMS(cms[0], cms[1], seed=seed, ctx=ctx) if cms is not None else None
+    ctx = ctx or _lib.default_context()
+    L = _lib.lib()
+    if hll is not None:
+        _lib.check(L.nkv_hll_add_records(ctx.h, p_buf, buf.size, p_sizes, sizes.size, hll.P, hll._reg.ctypes.data),
+                   "key sketches: HLL")
+    if cm is not None:
+        _lib.check(L.nkv_cms_insert_records(ctx.h, p_buf, buf.size, p_sizes, sizes.size, cm.M, cm.K, cm.HashSeeds[0],
+                                            cm._table.ctypes.data), "key sketches: CMS")
+    return hll, cm
 
 
 # ---------------------------------------------------------------------------
