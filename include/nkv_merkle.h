@@ -46,6 +46,10 @@
  *   cmsketch.New sizing     ds/cmsketch/cmsketch.go:18-24       nkv_cms_params
  *   (*CountMinSketch).Insert / Query  cmsketch.go:76-111        nkv_cms_insert[_records][_dev] /
  *                                                               nkv_cms_query[_dev]
+ *   record.Deserialize loop core/record/record.go:119-172,      nkv_frame_records_dev /
+ *     over a Data file      core/lsmtree/lsmtree.go:137-231     nkv_frame_records
+ *   wal.readEntireSegment   core/wal/wal.go:293-328             nkv_frame_records[_dev] with
+ *     (ReadAllSegments, ReadSegmentsInRange, ...)                 segment offsets
  *
  * Conventions
  *   - Every function returns an nkv_status (0 = NKV_OK) unless noted; nothing
@@ -79,8 +83,9 @@
  *       uint32_t arrays and filter words (d_crc, the encode's d_crc included,
  *         d_err, d_bits, the sketches' d_reg and d_table, nkv_cms_query_dev's
  *         d_out), 4-byte aligned;
- *       uint64_t arrays (d_rec_off, d_voff, d_vlen, d_stats, d_out_off, the
- *         encode's d_out_off included, d_out_src, d_hit), 8-byte aligned.
+ *       uint64_t arrays (d_rec_off, the frame's included, d_voff, d_vlen, d_stats,
+ *         d_out_off, the encode's d_out_off included, d_out_src, d_hit,
+ *         d_seg_first, d_seg_len), 8-byte aligned.
  *     nkv_leaf_hash*_dev write level 0 only (20 n bytes); nkv_tree_reduce_dev
  *     leaves level 0 as given; d_bits is ((m + 31) / 32) * 4 bytes; the merge
  *     and the sort write out_len bytes and n_out entries; nkv_index_summary_dev writes
@@ -90,8 +95,9 @@
  *     nkv_encode_records_dev writes *out_len bytes and n entries of d_out_off
  *     and of d_crc; d_reg is 2^p bytes and d_table 4 K M bytes, both updated
  *     in place and never touched outside those extents; nkv_cms_query_dev
- *     writes n entries of d_out.  Inputs are never
- *     written: values, record streams, offset and length arrays, the merge's
+ *     writes n entries of d_out; nkv_frame_records_dev writes *n_out entries
+ *     of d_rec_off, S + 1 of d_seg_first and S of d_seg_len.  Inputs are never
+ *     written: values, record streams, offset and length arrays, segment offsets, the merge's
  *     runs, the sort's log, the lookup's tables, filters and query keys, and the
  *     sketches' keys and the queried d_table are read in place
  *     (at any alignment where they are bytes).
@@ -247,10 +253,25 @@ int nkv_ctx_sync(nkv_ctx *ctx);
                                   merge them once at the end (a CMS table of more than 16384
                                   counters does not fit and takes 1).  Every value gives the same
                                   bytes */
+#define NKV_OPT_FRAME_PATH 22 /* nkv_frame_records[_dev]: 0 (default) = auto: the walk when the mean
+                                 segment (stream_len / segments) is shorter than 96 KiB, else
+                                 speculative; 1 = walk: one lane per segment follows its chain of
+                                 length prefixes; 2 = speculative: every byte position is tested as
+                                 a record start, the survivors' successor links are doubled from
+                                 the segment starts.  A speculative call
+                                 whose candidates do not fit NKV_OPT_FRAME_BUDGET (or number more
+                                 than 2^31 - 1, or none) takes the walk.  Every value gives the
+                                 same bytes */
+#define NKV_OPT_FRAME_BUDGET 23 /* bytes of device scratch a speculative frame call may use: 24 bytes
+                                   per 64 stream bytes for the marks plus about 17 per candidate
+                                   start; 0 (default) = auto: min(2 * stream_len, a quarter of the
+                                   free device memory) */
 int nkv_ctx_set_option(nkv_ctx *ctx, int key, int64_t value);
-/* Which path the latest host-buffer tree call of the context took */
+/* Which path the latest host-buffer tree call, or the latest frame call, of the context took */
 #define NKV_PATH_GRID 0  /* copies + leaf kernel + per-level reduce launches */
 #define NKV_PATH_SMALL 1 /* the one-launch small tree (NKV_OPT_SMALL_PATH) */
+#define NKV_PATH_FRAME_WALK 2        /* nkv_frame_records[_dev]: one lane per segment */
+#define NKV_PATH_FRAME_SPECULATIVE 3 /* nkv_frame_records[_dev]: mark, successor, doubling */
 int nkv_ctx_last_path(nkv_ctx *ctx, int *path);
 /* The resident small-tree service of the context (NKV_OPT_SMALL_PATH 3), for
  * diagnostics: out[0] doorbell (latest request), out[1] served (the latest the
@@ -618,6 +639,69 @@ int nkv_encode_records_dev(nkv_ctx *ctx, const nkv_puts *puts, void *d_out, uint
  * NULL it is a size query.  Synchronous. */
 int nkv_encode_records(nkv_ctx *ctx, const nkv_puts *puts, uint8_t *out, uint64_t out_cap,
                        uint64_t *out_rec_size, uint32_t *crc_out, uint64_t *out_len);
+
+/* ---- framing (core/record/record.go:119-172 in a loop) ----
+ * Every records entry above takes the record boundaries from its caller.  For
+ * bytes that come from disk the reference learns them by calling
+ * record.Deserialize until it reports EOF: over a Data file in lsmtree.merge
+ * (lsmtree.go:137-231) and over each WAL segment in wal.readEntireSegment
+ * (wal.go:293-328).  This entry is that loop in closed form, for a stream cut
+ * into S segments.
+ *
+ * Segment j is [d_seg_off[j], d_seg_off[j + 1]), the last one ends at
+ * stream_len; d_seg_off NULL with S = 0 means the one segment [0, stream_len).
+ * Offsets are non-decreasing and at most stream_len; equal neighbours are an
+ * empty segment; bytes before d_seg_off[0] belong to no segment and are never
+ * read as records.  Per segment, with p its start and end its end: the record
+ * at p is accepted iff 30 header bytes fit (end - p >= 30), KeySize <= end - p
+ * - 30 and ValueSize <= end - p - 30 - KeySize (no sum is formed before the
+ * compare); an accepted record advances p by 30 + KeySize + ValueSize; the
+ * first p that fails ends the segment and [p, end) is its tail -- Deserialize
+ * returning eof on io.EOF or io.ErrUnexpectedEOF at whichever field.  A record
+ * never crosses a segment end.
+ *
+ * Deviations from the reference: a KeySize or ValueSize so large that Go's make
+ * panics is a tail like any other size that does not fit; and checksums are
+ * not checked here (Deserialize panics on a bad one): nkv_record_crc_dev over
+ * the framed records does that.
+ *
+ * Device form.  d_rec_off (8-byte aligned, rec_cap entries) receives the
+ * accepted offsets, ascending, *n_out of them; d_seg_first (nullable, S + 1
+ * entries) the index of each segment's first record, d_seg_first[S] = n;
+ * d_seg_len (nullable, S entries) the bytes of whole records in each segment.
+ * With S = 0 that is the one entry d_seg_first[0] = n and no d_seg_len entry.
+ * stats: [0] n, [1] the sum of the segments' whole-record bytes, [2] the number
+ * of segments with a non-empty tail, [3] the lowest such segment (UINT64_MAX if
+ * none).  Exactly those extents are written.  With d_rec_off NULL the call is
+ * a size query: NKV_OK, *n_out and stats, nothing written.  The call
+ * synchronizes: the host reads the counts before any output is written.
+ *
+ * NKV_ERR_INVALID, with no device output written and the context usable, for:
+ * a null context, n_out or stats; a null stream with stream_len > 0; S > 0 with
+ * a null d_seg_off; segment offsets that decrease or pass stream_len (a kernel
+ * checks them before any kernel follows one); n or S above 2^31 - 1; rec_cap <
+ * n (*n_out and stats still reported, so the caller can retry); NKV_FRAME_STRICT
+ * with stats[2] > 0 (*n_out and stats still reported: stats[1] is where a
+ * one-segment stream's tail starts).  stream_len = 0 gives NKV_OK with n = 0.
+ * Under NKV_TIMING_EVENTS the "leaf" interval is mark, scans and successor
+ * (walk: the count pass and its scan), the "reduce" interval the doubling
+ * rounds and the compaction (walk: the write pass).  NKV_OPT_FRAME_PATH picks
+ * the path, NKV_OPT_FRAME_BUDGET bounds the speculative path's scratch. */
+#define NKV_FRAME_STRICT 1  /* any tail is NKV_ERR_INVALID (a Data table); without it tails are
+                               dropped as Deserialize's EOF drops them (a WAL) */
+int nkv_frame_records_dev(nkv_ctx *ctx, const void *d_stream, uint64_t stream_len,
+                          const uint64_t *d_seg_off, uint64_t S, int flags, uint64_t *d_rec_off,
+                          uint64_t rec_cap, uint64_t *d_seg_first, uint64_t *d_seg_len,
+                          uint64_t *n_out, uint64_t stats[4]);
+/* Host-memory form: uploads, runs the device form and returns the TotalSize of
+ * each record in rec_size_out (rec_cap entries) instead of offsets; with tails
+ * dropped, the sizes of segment j add up to seg_len_out[j].  seg_first_out
+ * (S + 1 entries) and seg_len_out (S entries) are nullable; rec_size_out NULL
+ * is the size query.  Synchronous. */
+int nkv_frame_records(nkv_ctx *ctx, const uint8_t *stream, uint64_t stream_len,
+                      const uint64_t *seg_off, uint64_t S, int flags, uint64_t *rec_size_out,
+                      uint64_t rec_cap, uint64_t *seg_first_out, uint64_t *seg_len_out,
+                      uint64_t *n_out, uint64_t stats[4]);
 
 /* ---- sketches: HyperLogLog (ds/hll) and Count-Min Sketch (ds/cmsketch) ----
  * The only typed values the reference's engine knows (WrapperEngine.PutHLL /

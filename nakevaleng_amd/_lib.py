@@ -39,12 +39,17 @@ NKV_OPT_SIDE_GATE = 18
 NKV_OPT_QUEUE_PAIR = 19  # retired: accepts only 0
 NKV_OPT_SERVICE_MAILBOX = 20
 NKV_OPT_SKETCH_PATH = 21  # 0 auto, 1 direct global atomics, 2 workgroup-private copies in LDS
+NKV_OPT_FRAME_PATH = 22  # 0 auto, 1 walk (one lane per segment), 2 speculative (mark, successor, doubling)
+NKV_OPT_FRAME_BUDGET = 23  # bytes of scratch a speculative frame call may use (0 = auto)
+NKV_FRAME_STRICT = 1
 NKV_HLL_MIN_PRECISION = 4
 NKV_HLL_MAX_PRECISION = 16
 NKV_HLL_ESTIMATE_REFERENCE = 0
 NKV_HLL_ESTIMATE_STANDARD = 1
 NKV_PATH_GRID = 0
 NKV_PATH_SMALL = 1
+NKV_PATH_FRAME_WALK = 2
+NKV_PATH_FRAME_SPECULATIVE = 3
 NKV_OPT_DEEP_PREFETCH = 3  # retired: accepts only 3
 NKV_OPT_QUEUE_RING = 9  # retired: accepts only 13
 NKV_ABI_VERSION = 1  # include/nkv_merkle.h
@@ -180,6 +185,8 @@ SIGNATURES = {
     "nkv_sort_records": (_int, [_vp, _vp, _u64, _vp, _u64, _vp, _u64, _vp, _u64p, _u64p]),
     "nkv_encode_records_dev": (_int, [_vp, ctypes.POINTER(NkvPuts), _vp, _u64, _vp, _vp, _u64p]),
     "nkv_encode_records": (_int, [_vp, ctypes.POINTER(NkvPuts), _vp, _u64, _vp, _vp, _u64p]),
+    "nkv_frame_records_dev": (_int, [_vp, _vp, _u64, _vp, _u64, _int, _vp, _u64, _vp, _vp, _u64p, _u64p]),
+    "nkv_frame_records": (_int, [_vp, _vp, _u64, _vp, _u64, _int, _vp, _u64, _vp, _vp, _u64p, _u64p]),
     "nkv_hll_add_dev": (_int, [_vp, _vp, _vp, _vp, _u64, _int, _vp]),
     "nkv_hll_add_records_dev": (_int, [_vp, _vp, _u64, _vp, _u64, _int, _vp]),
     "nkv_cms_insert_dev": (_int, [_vp, _vp, _vp, _vp, _u64, _u32, _u32, _u32, _vp]),

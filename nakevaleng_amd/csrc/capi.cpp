@@ -912,7 +912,7 @@ void nkv_ctx_destroy(nkv_ctx* c) {
     for (DevBuf* b : {&c->d_data, &c->d_off, &c->d_len, &c->d_nodes, &c->d_img, &c->d_tmp,
                       &c->d_err, &c->d_aux, &c->d_keys, &c->d_perm, &c->d_stmp, &c->d_queue, &c->d_stats,
                       &c->d_range, &c->d_part, &c->d_tmp2, &c->d_flags, &c->d_clk, &c->d_sin, &c->d_sout,
-                      &c->d_small, &c->d_ticket})
+                      &c->d_small, &c->d_ticket, &c->d_frame})
         if (b->p) (void)hipFree(b->p);
     for (nkv_ctx::Pinned* blk : c->pinned) {
         if (blk->d_arena.p) (void)hipFree(blk->d_arena.p);
@@ -987,6 +987,14 @@ int nkv_ctx_set_option(nkv_ctx* c, int key, int64_t value) try {
         case NKV_OPT_SKETCH_PATH:
             if (value < 0 || value > 2) return NKV_ERR_INVALID;
             c->sketch_path = int(value);
+            return NKV_OK;
+        case NKV_OPT_FRAME_PATH:
+            if (value < 0 || value > 2) return NKV_ERR_INVALID;
+            c->frame_path = int(value);
+            return NKV_OK;
+        case NKV_OPT_FRAME_BUDGET:
+            if (value < 0) return NKV_ERR_INVALID;
+            c->frame_budget = uint64_t(value);
             return NKV_OK;
         case NKV_OPT_HOST_THREADS:
             if (value < 0 || value > 256) return NKV_ERR_INVALID;

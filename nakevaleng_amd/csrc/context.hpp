@@ -162,6 +162,8 @@ struct nkv_ctx {
     int queue_waves = 3;    // NKV_OPT_QUEUE_WAVES
     int bloom_path = 2;     // NKV_OPT_BLOOM_PATH
     int sketch_path = 0;    // NKV_OPT_SKETCH_PATH
+    int frame_path = 0;     // NKV_OPT_FRAME_PATH
+    uint64_t frame_budget = 0;  // NKV_OPT_FRAME_BUDGET (0 = auto)
     int crc_load = 0;       // NKV_OPT_CRC_LOAD
     int records_fused = 1;  // NKV_OPT_RECORDS_FUSED
     int table_lanes = 2;    // NKV_OPT_TABLE_LANES
@@ -181,7 +183,8 @@ struct nkv_ctx {
     bool host_timed = false;
     nkv::DevBuf d_data, d_off, d_len, d_nodes, d_img, d_tmp, d_err, d_aux, d_keys, d_perm, d_stmp, d_queue,
         d_stats, d_range, d_part, d_tmp2, d_flags, d_clk,
-        d_ticket;  // k_len_range's ticket (zeroed when allocated; each launch leaves it zero)
+        d_ticket,  // k_len_range's ticket (zeroed when allocated; each launch leaves it zero)
+        d_frame;   // the speculative frame path's per-node scratch (d_keys is not free: the length sort keeps zeros in it)
     int flag_set = 0;  // which of the two pass-flag sets in d_flags the next records call uses
     // the length sort's bucket totals may be non-zero (a sort was cut short):
     // the next sort clears them first (internal.hpp sort_head_words)
@@ -226,7 +229,7 @@ struct nkv_ctx {
     uint8_t* h_sout = nullptr;
     size_t h_sin_cap = 0, h_sout_cap = 0;
     nkv::DevBuf d_sin, d_sout, d_small;
-    int last_path = 0;  // NKV_PATH_* of the latest host-buffer tree call
+    int last_path = 0;  // NKV_PATH_* of the latest host-buffer tree call or frame call
     uint32_t small_seq = 0;  // the small-tree kernel's completion word (per call)
     // NKV_OPT_SMALL_PATH 3: the resident service's mailbox and stream (created
     // on first use; the kernel leaves after kSvcIdleUs without a request or at

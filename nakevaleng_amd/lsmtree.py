@@ -20,6 +20,9 @@ flush_puts() starts one step earlier, from the keys and values themselves: it
 encodes the write log on the device (nkv_encode_records_dev, record.New /
 ToBytes) and goes on as flush_log does, with no host serialization.
 
+recover() starts from WAL segments that are only bytes: one upload, the record
+boundaries found on the device (nkv_frame_records_dev), then flush_log's steps.
+
 The read side: upload_table() keeps a Data table (and its filter) resident, and
 get_many() answers a batch of keys over resident tables in search order
 (nkv_lookup_dev, nkv_lookup_values_dev), the disk part of the engine's get.
@@ -401,6 +404,92 @@ def _flush_tail(ctx, dev_index, stream, d_log, nbytes, d_off, n, seed, false_pos
                                                ctypes.byref(n_out), ctypes.byref(out_len)), "memtable flush")
     return _table_secondaries(ctx, dev_index, stream, d_out, d_out_off, d_out_src, n_out.value, out_len.value,
                               "flush", seed, false_positive_rate, summary_page_size, resident)
+
+
+def recover(segments, device=None, **flush_kwargs):
+    """WAL replay into the memtable flush from one upload of the segments' bytes:
+    what the engine does at start with WAL.ReadAllSegments (wal.go:262-290)
+    and Memtable.Add / Flush, with no host pass over the records.  The listed
+    segments are concatenated and uploaded once; their records are framed on
+    the device (nkv_frame_records_dev: whole records only, a torn tail dropped
+    as readEntireSegment's Deserialize loop drops it); every record's Crc is
+    checked (nkv_record_crc_dev; a bad one raises record.verify's "Bad Record
+    checksum" ValueError, where Deserialize panics); then flush_log's tail: the
+    flush (nkv_sort_records_dev) and the flushed table's tree, filter, Index
+    and Summary.  `flush_kwargs` are flush_log's seed, false_positive_rate,
+    summary_page_size and resident, and so is the return value.
+
+    The flush refuses a log with gaps.  A tail behind the last record costs
+    nothing: the framed length is passed instead of the uploaded one.  A tail
+    with records behind it (a torn segment in the middle, which the WAL itself
+    never writes) is the rare path: the segment lengths come back to the host,
+    the gaps are closed there and the log is uploaded a second time.  No
+    records at all raise MerkleTreeError, as flush_log does."""
+    import ctypes
+    import torch
+    from . import _lib, wal
+    from .merkletree import MerkleTreeError
+    data, seg_off = wal.concat_segments(segments)
+    S, nbytes = int(seg_off.size), len(data)
+    if S == 0 or nbytes == 0:
+        raise MerkleTreeError("cannot build Merkle Tree from 0 nodes")
+    dev_index = rank_device(device)
+    ctx = _lib.default_context(dev_index)
+    L = _lib.lib()
+    dev = torch.device("cuda", dev_index)
+
+    def up(a):
+        return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).copy()).to(dev)
+
+    def u8(nb):
+        return torch.zeros(max(int(nb), 16), dtype=torch.uint8, device=dev)
+
+    def u64(t, count):
+        return t.cpu().numpy().view(np.uint64)[:count].copy()
+
+    stream = torch.cuda.current_stream(dev)
+    with ctx.on_stream(stream.cuda_stream):
+        d_data, d_seg = up(np.frombuffer(data, np.uint8)), up(seg_off)
+        cap = nbytes // 30
+        d_off, d_first, d_len = u8(8 * cap), u8(8 * (S + 1)), u8(8 * S)
+        n_out, stats = ctypes.c_uint64(0), (ctypes.c_uint64 * 4)()
+        _lib.check(L.nkv_frame_records_dev(ctx.h, d_data.data_ptr(), nbytes, d_seg.data_ptr(), S, 0,
+                                           d_off.data_ptr(), cap, d_first.data_ptr(), d_len.data_ptr(),
+                                           ctypes.byref(n_out), stats), "WAL replay: frame")
+        n, framed, tails, lowest = int(n_out.value), int(stats[1]), int(stats[2]), int(stats[3])
+        if n == 0:
+            raise MerkleTreeError("cannot build Merkle Tree from 0 nodes")
+        log_len = nbytes
+        if tails:
+            first = u64(d_first, S + 1)
+            if tails == 1 and int(first[lowest + 1]) == n:
+                log_len = framed  # the one tail lies behind the last record
+            else:  # rare: records behind a tail
+                seg_len, off = u64(d_len, S), u64(d_off, n)
+                ends = np.append(seg_off[1:], np.uint64(nbytes))
+                gap = (ends - seg_off) - seg_len  # every segment's tail
+                shift = np.cumsum(gap) - gap      # the tails in front of each segment
+                off -= np.repeat(shift, np.diff(first).astype(np.int64)).astype(np.uint64)
+                data = wal.close_gaps(data, seg_off, seg_len)
+                log_len = len(data)
+                assert log_len == framed
+                d_data = up(np.frombuffer(data, np.uint8))
+                d_off = up(off)
+        d_crc, d_stats = u8(4 * n), u8(24)
+        _lib.check(L.nkv_record_crc_dev(ctx.h, d_data.data_ptr(), log_len, d_off.data_ptr(), n, d_crc.data_ptr(),
+                                        d_stats.data_ptr()), "WAL replay: checksums")
+        bad, bad_first, hdr = d_stats.cpu().numpy().view(np.uint64)[:3].tolist()
+        if hdr:
+            raise _lib.NkvError(_lib.NKV_ERR_INVALID, "WAL replay: checksums")
+        if bad:
+            got = int(d_crc.cpu().numpy().view(np.uint32)[bad_first])
+            at = int(u64(d_off, n)[bad_first])
+            stored = int(np.frombuffer(data, "<u4", 1, at)[0])
+            raise ValueError(f"Bad Record checksum (got {got}, expected {stored})")
+        return _flush_tail(ctx, dev_index, stream, d_data, log_len, d_off, n,
+                           flush_kwargs.pop("seed", None), flush_kwargs.pop("false_positive_rate", 0.01),
+                           flush_kwargs.pop("summary_page_size", None), flush_kwargs.pop("resident", False),
+                           **flush_kwargs)
 
 
 def flush_puts(keys, values, timestamps=None, status=None, type_info=None, device=None, seed: Optional[int] = None,

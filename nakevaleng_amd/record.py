@@ -187,3 +187,58 @@ def verify(stream, rec_sizes, ctx=None) -> np.ndarray:
         stored = _HDR.unpack_from(bytes(stream), off)[0]
         raise ValueError(f"Bad Record checksum (got {int(crc[first])}, expected {stored})")
     return crc
+
+
+def frame(stream, segments=None, strict: bool = False, ctx=None):
+    """The record boundaries of raw bytes on the device (nkv_frame_records): the
+    loop of record.Deserialize (record.go:119-172) that the reference runs over
+    a Data file (lsmtree.go:137-231) and over every WAL segment (wal.go:293-328).
+    `segments` (optional) lists the segments' start offsets, non-decreasing;
+    None is the one segment that is the whole stream.  A record never crosses a
+    segment's end, and what is left of a segment behind its last whole record
+    is its tail: dropped, as Deserialize's eof drops it, or with `strict`
+    refused with a ValueError that names where the first tail starts.
+
+    Returns (rec_sizes, seg_first, seg_len, stats): each record's TotalSize,
+    the index of every segment's first record with n appended, the bytes of
+    whole records in every segment, and stats = [n, sum of seg_len, segments
+    with a tail, the lowest such segment or 2**64 - 1].  Checksums are not
+    checked here (record.verify does that)."""
+    import ctypes
+    from nakevaleng_amd import _lib
+    ctx = ctx or _lib.default_context()
+    buf = np.frombuffer(bytes(stream), np.uint8) if not isinstance(stream, np.ndarray) else stream
+    buf = np.ascontiguousarray(buf, dtype=np.uint8)
+    L = buf.size
+    seg = None if segments is None else np.ascontiguousarray(segments, dtype=np.uint64)
+    S = 0 if seg is None else int(seg.size)
+    if seg is not None and S == 0:
+        raise ValueError("frame: an empty list of segments (None is the whole stream)")
+    f = _lib.lib().nkv_frame_records
+    n_out, stats = ctypes.c_uint64(0), (ctypes.c_uint64 * 4)()
+    p_buf = buf.ctypes.data if L else None
+    p_seg = seg.ctypes.data if S else None
+    flags = _lib.NKV_FRAME_STRICT if strict else 0
+
+    def refused():
+        if strict and stats[2]:
+            j = int(stats[3])
+            at = int(stats[1]) if S == 0 else None
+            where = f"at byte {at}" if at is not None else f"in segment {j}"
+            return ValueError(f"frame: {int(stats[2])} segment(s) end in bytes that are no whole record, "
+                              f"the first {where}")
+        return _lib.NkvError(_lib.NKV_ERR_INVALID, "frame")
+
+    cap = L // HEADER_SIZE  # a record spends at least its header
+    sizes, first, seg_len = np.zeros(cap + 1, np.uint64), np.zeros(S + 2, np.uint64), np.zeros(S + 1, np.uint64)
+    rc = f(ctx.h, p_buf, L, p_seg, S, flags, sizes.ctypes.data, cap, first.ctypes.data, seg_len.ctypes.data,
+           ctypes.byref(n_out), stats)
+    if rc == _lib.NKV_ERR_INVALID:
+        raise refused()
+    _lib.check(rc, "frame")
+    n = int(n_out.value)
+    if S == 0:  # the one segment, as a caller who listed it would get it
+        first, seg_len = np.asarray([0, n], np.uint64), np.asarray([stats[1]], np.uint64)
+    else:
+        first, seg_len = first[:S + 1].copy(), seg_len[:S].copy()
+    return sizes[:n].copy(), first, seg_len, [int(x) for x in stats]

@@ -13,6 +13,8 @@
   make_table_secondaries_from_records   MakeTableSecondaries over a serialized
                              Data table: Index, Summary and Metadata files
                              (and the filter's bits) from one upload
+  open_data_table            the Deserialize loop lsmtree.merge runs over a Data file
+                             (lsmtree.go:137-231): the records' sizes from the bytes alone
   table_filename             util/filename.Table             filename.go:58-65, 300-309
 
 What remains outside this path is the Data file itself and the Filter's gob
@@ -41,6 +43,18 @@ def table_filename(path: str, dbname: str, level: int, run: int, filetype: str =
     if run < 0:
         raise ValueError("Run must be a non-negative integer!")
     return f"{path}{dbname}-{level}-{run}-{filetype}.db"
+
+
+def open_data_table(data, device: Optional[int] = None):
+    """A Data table that is only bytes (a Data file read back from disk) as the
+    Table = (stream, RecSize array) every records entry takes: the record
+    boundaries are found on the device (record.frame, strict).  A Data file
+    holds whole records and nothing else, so bytes behind the last whole record
+    raise ValueError naming the offset at which they start."""
+    from . import record
+    data = bytes(data)
+    sizes, _, _, _ = record.frame(data, strict=True, ctx=_lib.default_context(device))
+    return data, sizes
 
 
 def make_metadata(path: str, dbname: str, level: int, run: int, records: Iterable[Record]) -> MerkleTree:
