@@ -20,7 +20,7 @@ CSRC = os.path.join(PKG, "csrc")
 SO = os.path.join(PKG, "libnkvmerkle.so")
 SOURCES = ["leaf.hip", "reduce.hip", "small_tree.hip", "plan.hip", "crc.hip", "bloom.hip", "merge.hip",
            "memtable.hip", "index.hip", "lookup.hip", "encode.hip", "sketch.hip", "frame.hip",
-           "capi.cpp",
+           "context.cpp", "stage.cpp", "tree.cpp", "small_host.cpp",
            "group.cpp", "host_stage.cpp"]
 HEADERS = ["internal.hpp", "context.hpp", "sha1_dev.hpp", "sha1_feed_dev.hpp", "tree_dev.hpp", "host_stage.hpp",
            "crc_dev.hpp", "murmur_dev.hpp", "bytes_dev.hpp", "merge_copy_dev.hpp", "record_dev.hpp"]

@@ -18,7 +18,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "internal.hpp"  // record_dev.hpp: header_in, ld_le64, kHdr, kAtKeySize
+#include <cmath>
+
+#include "context.hpp"  // internal.hpp -> record_dev.hpp: header_in, ld_le64, kHdr, kAtKeySize
 #include "murmur_dev.hpp"  // mm_states, mm_fmix, fastmod_u32, kBloomMaxK
 
 namespace nkv {
@@ -188,7 +190,10 @@ __global__ __launch_bounds__(kBloomBlock) void k_bloom_apply(const uint32_t* __r
     }
 }
 
-uint64_t bloom_ranges_scratch_words(uint64_t n, uint32_t m, uint32_t k) {
+// Range-privatised insert (mode 0 = keys at base + off[i], len[i]; 1 = keys of
+// the records at base + off[i]); its scratch in u32 (0 = not applicable: more
+// than 4096 ranges of 32768 bits, or n * k >= 2^32).
+static uint64_t bloom_ranges_scratch_words(uint64_t n, uint32_t m, uint32_t k) {
     const uint64_t nranges = (uint64_t(m) + (1u << kBloomRangeShift) - 1) >> kBloomRangeShift;
     const uint64_t tiles = (n + uint64_t(kBloomBlock) * kBloomTileKeys - 1) / (uint64_t(kBloomBlock) * kBloomTileKeys);
     if (nranges > kBloomMaxRanges || n * k > 0xFFFFFFFFull) return 0;  // the atomic kernel serves these
@@ -196,7 +201,7 @@ uint64_t bloom_ranges_scratch_words(uint64_t n, uint32_t m, uint32_t k) {
     return h + scan_sums_words(h) + n * k;
 }
 
-hipError_t launch_bloom_ranges(int mode, const uint8_t* base, const uint64_t* off, const uint64_t* len,
+static hipError_t launch_bloom_ranges(int mode, const uint8_t* base, const uint64_t* off, const uint64_t* len,
                                uint64_t stream_len, uint64_t n, uint32_t m, uint32_t k, uint32_t seed0,
                                uint32_t* bits, unsigned int* err, uint32_t* scratch, hipStream_t s) {
     if (n == 0 || k == 0) return hipSuccess;
@@ -357,7 +362,9 @@ static uint32_t bloom_stage_kpt(uint32_t k, uint32_t nranges) {
     return kpt < 32u ? kpt : 32u;
 }
 
-uint64_t bloom_staged_scratch_words(uint64_t n, uint32_t m, uint32_t k) {
+// Staged insert (one hash pass; mode as above); its scratch in u32 (0 = not
+// applicable: k > 32 or more than 4096 ranges).
+static uint64_t bloom_staged_scratch_words(uint64_t n, uint32_t m, uint32_t k) {
     const uint64_t nranges = (uint64_t(m) + (1u << kBloomRangeShift) - 1) >> kBloomRangeShift;
     if (nranges > kBloomMaxRanges) return 0;
     const uint32_t kpt = bloom_stage_kpt(k, uint32_t(nranges));
@@ -366,7 +373,7 @@ uint64_t bloom_staged_scratch_words(uint64_t n, uint32_t m, uint32_t k) {
     return tiles * kpt * k * kBloomBlock + 2 * tiles * nranges;
 }
 
-hipError_t launch_bloom_staged(int mode, const uint8_t* base, const uint64_t* off, const uint64_t* len,
+static hipError_t launch_bloom_staged(int mode, const uint8_t* base, const uint64_t* off, const uint64_t* len,
                                uint64_t stream_len, uint64_t n, uint32_t m, uint32_t k, uint32_t seed0,
                                uint32_t* bits, unsigned int* err, uint32_t* scratch, hipStream_t s) {
     if (n == 0 || k == 0) return hipSuccess;
@@ -392,7 +399,9 @@ hipError_t launch_bloom_staged(int mode, const uint8_t* base, const uint64_t* of
     return hipGetLastError();
 }
 
-hipError_t launch_bloom(int mode, bool query, const uint8_t* base, const uint64_t* off, const uint64_t* len,
+// One device atomicOr per bit (mode as above).  query: out[i] = all k bits set;
+// else OR the bits in.
+static hipError_t launch_bloom(int mode, bool query, const uint8_t* base, const uint64_t* off, const uint64_t* len,
                         uint64_t stream_len, uint64_t n, uint32_t m, uint32_t k, uint32_t seed0, uint32_t* bits,
                         uint8_t* out, unsigned int* err, hipStream_t s) {
     if (n == 0 || k == 0) return hipSuccess;
@@ -411,4 +420,124 @@ hipError_t launch_bloom(int mode, bool query, const uint8_t* base, const uint64_
     return hipGetLastError();
 }
 
+// Filter inserts: the staged or the range-privatised build for batches of at
+// least 4096 keys when its scratch applies (NKV_OPT_BLOOM_PATH), else one
+// device atomicOr per bit.
+static int bloom_insert(nkv_ctx* c, int mode, const uint8_t* base, const uint64_t* off, const uint64_t* len,
+                        uint64_t stream_len, uint64_t n, uint32_t m, uint32_t k, uint32_t seed0, uint32_t* bits,
+                        unsigned int* err) {
+    const uint64_t staged = c->bloom_path == 2 && n >= 4096 ? bloom_staged_scratch_words(n, m, k) : 0;
+    if (staged) {
+        TRY(grow(c->d_tmp, 4 * staged));
+        return st(launch_bloom_staged(mode, base, off, len, stream_len, n, m, k, seed0, bits, err,
+                                      static_cast<uint32_t*>(c->d_tmp.p), c->stream));
+    }
+    const uint64_t words = c->bloom_path >= 1 && n >= 4096 ? bloom_ranges_scratch_words(n, m, k) : 0;
+    if (words) {
+        TRY(grow(c->d_tmp, 4 * words));
+        return st(launch_bloom_ranges(mode, base, off, len, stream_len, n, m, k, seed0, bits, err,
+                                      static_cast<uint32_t*>(c->d_tmp.p), c->stream));
+    }
+    return st(launch_bloom(mode, false, base, off, len, stream_len, n, m, k, seed0, bits, nullptr, err, c->stream));
+}
+
+// The host forms' filter: m bits as zeroed words in d_img.
+static int filter_image(nkv_ctx* c, uint32_t m) {
+    const uint64_t wbytes = 4 * ((uint64_t(m) + 31) / 32);
+    TRY(grow(c->d_img, wbytes));
+    HIPTRY(hipMemsetAsync(c->d_img.p, 0, wbytes, c->stream));
+    return NKV_OK;
+}
+
+static int filter_out(nkv_ctx* c, uint32_t m, uint8_t* bits_out) {
+    HIPTRY(c->stage.download(bits_out, static_cast<const uint8_t*>(c->d_img.p), (uint64_t(m) + 7) / 8, c->stream));
+    return st(hipStreamSynchronize(c->stream));
+}
+
 }  // namespace nkv
+
+using namespace nkv;
+
+// ---------------------------------------------------------------------------
+// C-ABI
+
+extern "C" {
+
+int nkv_bloom_params(uint64_t n, double p, uint32_t* m, uint32_t* k) try {
+    if (!m || !k || n == 0 || !(p > 0.0 && p < 1.0)) return NKV_ERR_INVALID;
+    const double ln2 = std::log(2.0);  // bloomfilter.go:18-24
+    const double mm = std::ceil(double(n) * std::fabs(std::log(p)) / std::pow(ln2, 2.0));
+    if (!(mm >= 1.0 && mm <= 4294967295.0)) return NKV_ERR_INVALID;
+    *m = uint32_t(mm);
+    *k = uint32_t(std::ceil((double(*m) / double(n)) * ln2));
+    return NKV_OK;
+} NKV_CATCH
+
+int nkv_bloom_insert_dev(nkv_ctx* c, const void* d_keys, const uint64_t* d_off, const uint64_t* d_len, uint64_t n,
+                         uint32_t m, uint32_t k, uint32_t seed0, void* d_bits) try {
+    TRY(bind(c));
+    if (n > kMaxN) return NKV_ERR_INVALID;
+    if (m == 0 || !d_bits) return NKV_ERR_INVALID;
+    if (n == 0) return NKV_OK;
+    if (!d_keys || !d_off || !d_len) return NKV_ERR_INVALID;
+    return bloom_insert(c, 0, static_cast<const uint8_t*>(d_keys), d_off, d_len, 0, n, m, k, seed0,
+                        static_cast<uint32_t*>(d_bits), nullptr);
+} NKV_CATCH
+
+int nkv_bloom_insert_records_dev(nkv_ctx* c, const void* d_stream, uint64_t stream_len, const uint64_t* d_rec_off,
+                                 uint64_t n, uint32_t m, uint32_t k, uint32_t seed0, void* d_bits) try {
+    TRY(bind(c));
+    if (n > kMaxN) return NKV_ERR_INVALID;
+    if (m == 0 || !d_bits) return NKV_ERR_INVALID;
+    if (n == 0) return NKV_OK;
+    if (!d_stream || !d_rec_off) return NKV_ERR_INVALID;
+    TRY(grow(c->d_err, 4));
+    unsigned int* err = static_cast<unsigned int*>(c->d_err.p);
+    HIPTRY(hipMemsetAsync(err, 0, 4, c->stream));
+    TRY(bloom_insert(c, 1, static_cast<const uint8_t*>(d_stream), d_rec_off, nullptr, stream_len, n, m, k, seed0,
+                     static_cast<uint32_t*>(d_bits), err));
+    return read_verdict(c, err);
+} NKV_CATCH
+
+int nkv_bloom_query_dev(nkv_ctx* c, const void* d_keys, const uint64_t* d_off, const uint64_t* d_len, uint64_t n,
+                        uint32_t m, uint32_t k, uint32_t seed0, const void* d_bits, uint8_t* d_out) try {
+    TRY(bind(c));
+    if (n > kMaxN) return NKV_ERR_INVALID;
+    if (m == 0 || !d_bits) return NKV_ERR_INVALID;
+    if (n == 0) return NKV_OK;
+    if (!d_keys || !d_off || !d_len || !d_out) return NKV_ERR_INVALID;
+    if (k == 0) return st(hipMemsetAsync(d_out, 1, n, c->stream));  // Query with no hashes: true
+    return st(launch_bloom(0, true, static_cast<const uint8_t*>(d_keys), d_off, d_len, 0, n, m, k, seed0,
+                           const_cast<uint32_t*>(static_cast<const uint32_t*>(d_bits)), d_out, nullptr,
+                           c->stream));
+} NKV_CATCH
+
+int nkv_bloom_build(nkv_ctx* c, const uint8_t* keys, const uint64_t* off, const uint64_t* len, uint64_t n,
+                    uint32_t m, uint32_t k, uint32_t seed0, uint8_t* bits_out) try {
+    TRY(bind(c));
+    if (n > kMaxN) return NKV_ERR_INVALID;
+    if (m == 0 || !bits_out || (n && (!keys || !off || !len))) return NKV_ERR_INVALID;
+    TRY(filter_image(c, m));
+    if (n) {
+        TRY(stage_spans(c, keys, off, len, n));
+        TRY(nkv_bloom_insert_dev(c, c->d_data.p, static_cast<const uint64_t*>(c->d_off.p),
+                                 static_cast<const uint64_t*>(c->d_len.p), n, m, k, seed0, c->d_img.p));
+    }
+    return filter_out(c, m, bits_out);
+} NKV_CATCH
+
+int nkv_bloom_from_records(nkv_ctx* c, const uint8_t* stream, uint64_t stream_len, const uint64_t* rec_size,
+                           uint64_t n, uint32_t m, uint32_t k, uint32_t seed0, uint8_t* bits_out) try {
+    TRY(bind(c));
+    if (n > kMaxN) return NKV_ERR_INVALID;
+    if (m == 0 || !bits_out || (n && (!stream || !rec_size))) return NKV_ERR_INVALID;
+    TRY(filter_image(c, m));
+    if (n) {
+        const uint64_t* rec_off = nullptr;
+        TRY(stage_records(c, stream, stream_len, rec_size, n, &rec_off));
+        TRY(nkv_bloom_insert_records_dev(c, c->d_data.p, stream_len, rec_off, n, m, k, seed0, c->d_img.p));
+    }
+    return filter_out(c, m, bits_out);
+} NKV_CATCH
+
+}  // extern "C"

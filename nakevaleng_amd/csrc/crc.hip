@@ -33,8 +33,8 @@
 
 #include <algorithm>
 
+#include "context.hpp"  // internal.hpp -> record_dev.hpp: header_in, ld_le64, kHdr, kAt*
 #include "crc_dev.hpp"
-#include "internal.hpp"  // record_dev.hpp: header_in, ld_le64, kHdr, kAt*
 
 namespace nkv {
 
@@ -525,20 +525,87 @@ hipError_t launch_crc_spans(const uint8_t* base, const uint64_t* off, const uint
     return hipGetLastError();
 }
 
-hipError_t launch_record_crc(const uint8_t* stream, uint64_t stream_len, const uint64_t* rec_off, uint64_t n,
-                             uint32_t* out, unsigned long long* stats, int variant, hipStream_t s, Gate gate,
-                             bool init_stats) {
+// Records form (stats: 3 x u64, reset here to {0, UINT64_MAX, 0}); this unit's
+// entries are its only callers.
+static hipError_t launch_record_crc(const uint8_t* stream, uint64_t stream_len, const uint64_t* rec_off, uint64_t n,
+                                    uint32_t* out, unsigned long long* stats, int variant, hipStream_t s) {
     if (variant != 8) {
         const hipError_t e = lanes_layout_ok<true>();
         if (e != hipSuccess) return e;
     }
-    if (init_stats) {
-        hipError_t e = hipMemsetAsync(stats, 0, 3 * sizeof(unsigned long long), s);
-        if (e == hipSuccess) e = hipMemsetAsync(stats + 1, 0xFF, sizeof(unsigned long long), s);
-        if (e != hipSuccess) return e;
-    }
-    launch_crc<true>(variant, stream, rec_off, nullptr, stream_len, n, out, stats, s, gate);
+    hipError_t e = hipMemsetAsync(stats, 0, 3 * sizeof(unsigned long long), s);
+    if (e == hipSuccess) e = hipMemsetAsync(stats + 1, 0xFF, sizeof(unsigned long long), s);
+    if (e != hipSuccess) return e;
+    launch_crc<true>(variant, stream, rec_off, nullptr, stream_len, n, out, stats, s, Gate{});
     return hipGetLastError();
 }
 
 }  // namespace nkv
+
+using namespace nkv;
+
+// ---------------------------------------------------------------------------
+// C-ABI
+
+extern "C" {
+
+int nkv_crc32_dev(nkv_ctx* c, const void* d_base, const uint64_t* d_off, const uint64_t* d_len, uint64_t n,
+                  uint32_t* d_crc) try {
+    TRY(bind(c));
+    if (n > kMaxN) return NKV_ERR_INVALID;
+    if (n == 0) return NKV_OK;
+    if (!d_base || !d_off || !d_len || !d_crc) return NKV_ERR_INVALID;
+    return st(launch_crc_spans(static_cast<const uint8_t*>(d_base), d_off, d_len, n, d_crc, c->crc_load, c->stream));
+} NKV_CATCH
+
+int nkv_record_crc_dev(nkv_ctx* c, const void* d_stream, uint64_t stream_len, const uint64_t* d_rec_off,
+                       uint64_t n, uint32_t* d_crc, uint64_t* d_stats) try {
+    TRY(bind(c));
+    if (n > kMaxN) return NKV_ERR_INVALID;
+    if (!d_stream && n) return NKV_ERR_INVALID;
+    if (n && !d_rec_off) return NKV_ERR_INVALID;
+    if (n == 0) {
+        if (d_stats) {
+            HIPTRY(hipMemsetAsync(d_stats, 0, 24, c->stream));
+            HIPTRY(hipMemsetAsync(d_stats + 1, 0xFF, 8, c->stream));
+        }
+        return NKV_OK;
+    }
+    unsigned long long* stats = reinterpret_cast<unsigned long long*>(d_stats);
+    if (!stats) {
+        TRY(grow(c->d_stats, 24));
+        stats = static_cast<unsigned long long*>(c->d_stats.p);
+    }
+    return st(launch_record_crc(static_cast<const uint8_t*>(d_stream), stream_len, d_rec_off, n, d_crc, stats,
+                                c->crc_load, c->stream));
+} NKV_CATCH
+
+int nkv_record_crc(nkv_ctx* c, const uint8_t* stream, uint64_t stream_len, const uint64_t* rec_size,
+                   uint64_t n, uint32_t* crc_out, uint64_t* n_bad, uint64_t* first_bad) try {
+    TRY(bind(c));
+    if (n > kMaxN) return NKV_ERR_INVALID;
+    if (n_bad) *n_bad = 0;
+    if (first_bad) *first_bad = ~0ull;
+    if (n == 0) return NKV_OK;
+    if (!stream || !rec_size) return NKV_ERR_INVALID;
+    const uint64_t* rec_off = nullptr;
+    TRY(stage_records(c, stream, stream_len, rec_size, n, &rec_off));
+    DevBuf& crcs = c->d_off;  // n u32
+    TRY(grow(crcs, 4 * n));
+    TRY(grow(c->d_stats, 24));
+    uint32_t* d_crc = static_cast<uint32_t*>(crcs.p);
+    uint64_t* d_stats = static_cast<uint64_t*>(c->d_stats.p);
+    TRY(nkv_record_crc_dev(c, c->d_data.p, stream_len, rec_off, n, d_crc, d_stats));
+    // the rec_size copy in h_stage has been consumed once the stream reaches here
+    uint64_t* hs = static_cast<uint64_t*>(c->h_stage);
+    HIPTRY(hipMemcpyAsync(hs, d_stats, 24, hipMemcpyDeviceToHost, c->stream));
+    HIPTRY(hipStreamSynchronize(c->stream));
+    if (hs[2]) return NKV_ERR_INVALID;
+    if (n_bad) *n_bad = hs[0];
+    if (first_bad) *first_bad = hs[1];
+    if (crc_out) HIPTRY(c->stage.download(reinterpret_cast<uint8_t*>(crc_out), reinterpret_cast<const uint8_t*>(d_crc),
+                                          4 * n, c->stream));
+    return NKV_OK;
+} NKV_CATCH
+
+}  // extern "C"

@@ -416,7 +416,8 @@ int nkv_encode_records(nkv_ctx* c, const nkv_puts* puts, uint8_t* out, uint64_t 
     const uint64_t at_st = 5 * 8 * n, at_ty = at_st + n, at_keys = up16(at_ty + n),
                    at_vals = at_keys + up16(puts->keys_len), bytes = at_vals + up16(puts->vals_len);
     TRY(grow(c->d_data, bytes + 16));
-    TRY(grow(c->d_nodes, total));
+    DevBuf& log = c->d_nodes;  // the encoded write log
+    TRY(grow(log, total));
     TRY(grow(c->d_off, 8 * n));
     TRY(grow(c->d_len, 4 * n));
     uint8_t* d = static_cast<uint8_t*>(c->d_data.p);
@@ -446,9 +447,9 @@ int nkv_encode_records(nkv_ctx* c, const nkv_puts* puts, uint8_t* out, uint64_t 
     uint64_t* d_out_off = static_cast<uint64_t*>(c->d_off.p);
     uint32_t* d_crc = static_cast<uint32_t*>(c->d_len.p);
     uint64_t got = 0;
-    TRY(nkv_encode_records_dev(c, &dp, c->d_nodes.p, total, d_out_off, d_crc, &got));
+    TRY(nkv_encode_records_dev(c, &dp, log.p, total, d_out_off, d_crc, &got));
     if (crc_out) HIPTRY(hipMemcpyAsync(crc_out, d_crc, 4 * n, hipMemcpyDeviceToHost, c->stream));
-    return download_table(c, c->d_nodes.p, total, d_out_off, n, out, out_rec_size);  // the call's synchronize
+    return download_table(c, log.p, total, d_out_off, n, out, out_rec_size);  // the call's synchronize
 } NKV_CATCH
 
 }  // extern "C"

@@ -449,18 +449,11 @@ void nkv_group_destroy(nkv_group* grp) {
         if (cm) (void)ncclCommDestroy(cm);
     for (int i = 0; i < grp->g; ++i) {
         (void)hipSetDevice(grp->dev[i]);
-        for (DevBuf* b : {&grp->slot[i], &grp->gathered[i], &grp->levels[i], &grp->top[i]})
-            if (b->p) (void)hipFree(b->p);
         if (grp->ev[i]) (void)hipEventDestroy(grp->ev[i]);
         if (grp->ev2[i]) (void)hipEventDestroy(grp->ev2[i]);
     }
-    if (!grp->dev.empty()) {
-        (void)hipSetDevice(grp->dev[0]);
-        for (DevBuf* b : {&grp->full, &grp->img})
-            if (b->p) (void)hipFree(b->p);
-    }
     for (nkv_ctx* c : grp->ctx) nkv_ctx_destroy(c);
-    delete grp;
+    delete grp;  // its device buffers free themselves (hipFree takes a pointer of any device)
 }
 
 int nkv_group_peer_access(const nkv_group* grp, int i, int j, int* state) try {

@@ -269,7 +269,7 @@ int index_summary(nkv_ctx* c, const uint8_t* d_stream, uint64_t stream_len, cons
     *index_len = ilen;
     *summary_len = slen;
     if (query) return mark(c, 2);
-    if (own) {
+    if (own) {  // the host form: the Index image in d_nodes, the Summary in d_img
         if (index_cap >= ilen && summary_cap >= slen) {
             TRY(grow(c->d_nodes, ilen));
             TRY(grow(c->d_img, slen));

@@ -1,5 +1,7 @@
 // internal.hpp -- the constants and launcher declarations shared by the device
-// translation units (*.hip) and the C-ABI ones (capi.cpp, group.cpp).
+// translation units (*.hip) and the host ones (context.cpp, tree.cpp,
+// small_host.cpp, group.cpp).  A launcher whose callers all live in its own
+// unit is not declared here.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -128,16 +130,11 @@ uint64_t sort_head_words();
 // cw: words block 0 of the first launch copies before it reads the gate.
 hipError_t sort_by_length_desc(const uint64_t* len, uint64_t n, uint32_t* perm, uint32_t* hist, hipStream_t s,
                                Gate gate = Gate{}, QueueInit qi = QueueInit{}, CopyWords cw = CopyWords{});
-// crc.hip: CRC-32/IEEE of byte spans / of records' Key ++ Value (stats: 3 x u64,
-// initialised by the launcher).
+// crc.hip: CRC-32/IEEE of byte spans (encode.hip checksums its records with it).
 // variant: NKV_OPT_CRC_LOAD (0 = one lane per span, lane-private tables; 8 =
 // 16 lanes per span).
 hipError_t launch_crc_spans(const uint8_t* base, const uint64_t* off, const uint64_t* len, uint64_t n,
                             uint32_t* out, int variant, hipStream_t s);
-// init_stats: reset stats to {0, UINT64_MAX, 0} first (false: the caller did)
-hipError_t launch_record_crc(const uint8_t* stream, uint64_t stream_len, const uint64_t* rec_off, uint64_t n,
-                             uint32_t* out, unsigned long long* stats, int variant, hipStream_t s,
-                             Gate gate = Gate{}, bool init_stats = true);
 // The compaction read in one pass (leaf.hip k_leaf_verify): for the record at
 // stream + rec_off[i], its CRC of Key ++ Value into crc_out[i] (nullable),
 // checked against the stored Crc into stats as launch_record_crc does (stats
@@ -152,24 +149,6 @@ hipError_t launch_leaf_verify(const uint8_t* stream, uint64_t stream_len, const 
                               int policy, uint64_t* voff, uint64_t* vlen, uint8_t* nodes, uint32_t* crc_out,
                               unsigned long long* stats, unsigned int* range, uint32_t* part, hipStream_t s,
                               uint32_t* flags = nullptr, uint32_t* flags_next = nullptr);
-// bloom.hip: mode 0 = keys at base + off[i], len[i]; 1 = keys of the records at
-// base + off[i].  query: out[i] = all k bits set; else OR the bits in.
-hipError_t launch_bloom(int mode, bool query, const uint8_t* base, const uint64_t* off, const uint64_t* len,
-                        uint64_t stream_len, uint64_t n, uint32_t m, uint32_t k, uint32_t seed0, uint32_t* bits,
-                        uint8_t* out, unsigned int* err, hipStream_t s);
-// Range-privatised insert (mode as launch_bloom); scratch: bloom_ranges_scratch_words
-// u32 (0 = not applicable: more than 4096 ranges of 32768 bits, or n * k >= 2^32).
-uint64_t bloom_ranges_scratch_words(uint64_t n, uint32_t m, uint32_t k);
-hipError_t launch_bloom_ranges(int mode, const uint8_t* base, const uint64_t* off, const uint64_t* len,
-                               uint64_t stream_len, uint64_t n, uint32_t m, uint32_t k, uint32_t seed0,
-                               uint32_t* bits, unsigned int* err, uint32_t* scratch, hipStream_t s);
-// Staged insert (one hash pass; mode as launch_bloom); scratch:
-// bloom_staged_scratch_words u32 (0 = not applicable: k > 32 or more than
-// 4096 ranges).
-uint64_t bloom_staged_scratch_words(uint64_t n, uint32_t m, uint32_t k);
-hipError_t launch_bloom_staged(int mode, const uint8_t* base, const uint64_t* off, const uint64_t* len,
-                               uint64_t stream_len, uint64_t n, uint32_t m, uint32_t k, uint32_t seed0,
-                               uint32_t* bits, unsigned int* err, uint32_t* scratch, hipStream_t s);
 hipError_t launch_fill(uint8_t* buf, uint64_t nbytes, uint64_t seed, hipStream_t s);
 // One-launch small tree (small_tree.hip k_small_tree): desc = n (offset, length)
 // u64 pairs, value i at vals + offset (16-byte aligned); out receives

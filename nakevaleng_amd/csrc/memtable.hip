@@ -289,16 +289,17 @@ int nkv_sort_records(nkv_ctx* c, const uint8_t* log, uint64_t log_len, const uin
     TRY(grow(c->d_data, (log_len + 15) & ~uint64_t(15)));
     TRY(grow(c->d_len, 8 * n));
     TRY(grow(c->d_off, 8 * n));
-    TRY(grow(c->d_nodes, log_len));
-    TRY(grow(c->d_tmp2, 8 * n));
+    DevBuf& table = c->d_nodes;  // the flushed Data table
+    TRY(grow(table, log_len));
+    TRY(grow(c->d_rec_off, 8 * n));
     uint64_t* d_size = static_cast<uint64_t*>(c->d_len.p);
     uint64_t* d_off = static_cast<uint64_t*>(c->d_off.p);
-    uint64_t* d_out_off = static_cast<uint64_t*>(c->d_tmp2.p);
+    uint64_t* d_out_off = static_cast<uint64_t*>(c->d_rec_off.p);
     TRY(upload_records(c, log, log_len, rec_size, n, c->d_data.p, d_size, d_off));
-    TRY(nkv_sort_records_dev(c, c->d_data.p, log_len, d_off, n, c->d_nodes.p, log_len, d_out_off, nullptr, n_out,
+    TRY(nkv_sort_records_dev(c, c->d_data.p, log_len, d_off, n, table.p, log_len, d_out_off, nullptr, n_out,
                              out_len));
     if (*n_out == 0) return NKV_OK;
-    return download_table(c, c->d_nodes.p, *out_len, d_out_off, *n_out, out, out_rec_size);
+    return download_table(c, table.p, *out_len, d_out_off, *n_out, out, out_rec_size);
 } NKV_CATCH
 
 }  // extern "C"

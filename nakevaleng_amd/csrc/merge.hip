@@ -185,8 +185,7 @@ int nkv_merge_records_dev(nkv_ctx* c, const nkv_run* runs, int k, void* d_out, u
     if (!d_out || !d_out_off) return NKV_ERR_INVALID;
 
     // scratch: ten u64 arrays of N, the scan's temporary, and [err | n_out, out_len].
-    // The arrays live in d_stmp, which carries nothing from call to call (d_keys
-    // does: the length sort expects its head words left at zero).
+    // The arrays live in d_stmp (free scratch, context.hpp).
     Dense D;
     Slots S;
     const auto carve = [&](Carver k) {
@@ -247,12 +246,13 @@ int nkv_merge_records(nkv_ctx* c, const uint8_t* const* streams, const uint64_t*
     TRY(grow(c->d_data, padded));
     TRY(grow(c->d_len, 8 * N));
     TRY(grow(c->d_off, 8 * N));
-    TRY(grow(c->d_nodes, total));
-    TRY(grow(c->d_tmp2, 8 * N));
+    DevBuf& table = c->d_nodes;  // the merged Data table
+    TRY(grow(table, total));
+    TRY(grow(c->d_rec_off, 8 * N));
     uint8_t* d_in = static_cast<uint8_t*>(c->d_data.p);
     uint64_t* d_size = static_cast<uint64_t*>(c->d_len.p);
     uint64_t* d_off = static_cast<uint64_t*>(c->d_off.p);
-    uint64_t* d_out_off = static_cast<uint64_t*>(c->d_tmp2.p);
+    uint64_t* d_out_off = static_cast<uint64_t*>(c->d_rec_off.p);
     nkv_run runs[NKV_MERGE_MAX_RUNS];
     uint64_t base = 0;
     for (int r = 0; r < k; ++r) {
@@ -261,9 +261,9 @@ int nkv_merge_records(nkv_ctx* c, const uint8_t* const* streams, const uint64_t*
         TRY(upload_records(c, streams[r], stream_len[r], rec_size[r], n[r], d_in + at[r], d_size + base, d_off + base));
         base += n[r];
     }
-    TRY(nkv_merge_records_dev(c, runs, k, c->d_nodes.p, total, d_out_off, nullptr, n_out, out_len));
+    TRY(nkv_merge_records_dev(c, runs, k, table.p, total, d_out_off, nullptr, n_out, out_len));
     if (*n_out == 0) return NKV_OK;
-    return download_table(c, c->d_nodes.p, *out_len, d_out_off, *n_out, out, out_rec_size);
+    return download_table(c, table.p, *out_len, d_out_off, *n_out, out, out_rec_size);
 } NKV_CATCH
 
 }  // extern "C"

@@ -327,33 +327,6 @@ int cms_insert(nkv_ctx* c, int mode, const uint8_t* base, const uint64_t* off, c
 bool hll_p_ok(int p) { return p >= NKV_HLL_MIN_PRECISION && p <= NKV_HLL_MAX_PRECISION; }
 bool cms_shape_ok(uint32_t m, uint32_t k) { return m >= 1 && k >= 1 && uint64_t(m) * k <= 0x7FFFFFFFull; }
 
-// n host spans to d_data / d_off / d_len, as nkv_bloom_build stages them
-int stage_spans(nkv_ctx* c, const uint8_t* keys, const uint64_t* off, const uint64_t* len, uint64_t n) {
-    uint64_t total = 0;
-    for (uint64_t i = 0; i < n; ++i) total = std::max(total, off[i] + len[i]);
-    TRY(grow_host(c, 16 * n));
-    TRY(grow(c->d_data, total + 1));
-    TRY(grow(c->d_off, 8 * n));
-    TRY(grow(c->d_len, 8 * n));
-    uint8_t* h = static_cast<uint8_t*>(c->h_stage);
-    HIPTRY(c->stage.upload(keys, total, static_cast<uint8_t*>(c->d_data.p), c->stream));
-    memcpy(h, off, 8 * n);
-    memcpy(h + 8 * n, len, 8 * n);
-    HIPTRY(hipMemcpyAsync(c->d_off.p, h, 8 * n, hipMemcpyHostToDevice, c->stream));
-    HIPTRY(hipMemcpyAsync(c->d_len.p, h + 8 * n, 8 * n, hipMemcpyHostToDevice, c->stream));
-    return NKV_OK;
-}
-
-// a host stream and its record sizes to d_data / d_aux, the offsets into d_len
-int stage_records(nkv_ctx* c, const uint8_t* stream, uint64_t stream_len, const uint64_t* rec_size, uint64_t n,
-                  uint64_t** rec_off) {
-    if (!records_fit(rec_size, n, stream_len)) return NKV_ERR_INVALID;
-    TRY(stage_stream(c, stream, stream_len, c->d_data, rec_size, n, c->d_aux));
-    TRY(grow(c->d_len, 8 * n));
-    *rec_off = static_cast<uint64_t*>(c->d_len.p);
-    return nkv_record_offsets_dev(c, static_cast<const uint64_t*>(c->d_aux.p), n, *rec_off);
-}
-
 // the caller's register file or table to d_img and, after the work, back
 int image_in(nkv_ctx* c, const void* host, uint64_t bytes) {
     TRY(grow(c->d_img, bytes));
@@ -453,7 +426,7 @@ int nkv_hll_add_records(nkv_ctx* c, const uint8_t* stream, uint64_t stream_len, 
     if (n == 0) return NKV_OK;
     if (!stream || !rec_size) return NKV_ERR_INVALID;
     const uint64_t bytes = uint64_t(1) << p;
-    uint64_t* rec_off = nullptr;
+    const uint64_t* rec_off = nullptr;
     TRY(image_in(c, reg, bytes));
     TRY(stage_records(c, stream, stream_len, rec_size, n, &rec_off));
     TRY(nkv_hll_add_records_dev(c, c->d_data.p, stream_len, rec_off, n, p, c->d_img.p));
@@ -482,7 +455,7 @@ int nkv_cms_insert_records(nkv_ctx* c, const uint8_t* stream, uint64_t stream_le
     if (n == 0) return NKV_OK;
     if (!stream || !rec_size) return NKV_ERR_INVALID;
     const uint64_t bytes = 4 * uint64_t(m) * k;
-    uint64_t* rec_off = nullptr;
+    const uint64_t* rec_off = nullptr;
     TRY(image_in(c, table, bytes));
     TRY(stage_records(c, stream, stream_len, rec_size, n, &rec_off));
     TRY(nkv_cms_insert_records_dev(c, c->d_data.p, stream_len, rec_off, n, m, k, seed0,

@@ -14,7 +14,7 @@
 namespace nkv {
 
 // ---------------------------------------------------------------------------
-// tree shape helpers (device side; host side mirrors them in capi.cpp)
+// tree shape helpers (device side; host side mirrors them in context.hpp)
 
 __device__ __forceinline__ uint64_t lvl_count(uint64_t n, int L) {
     return L == 0 ? n : ((n - 1) >> L) + 1;  // ceil(n / 2^L), n >= 1

@@ -35,7 +35,7 @@ MERKLE_NODE_EMPTY = 1  # merklenode.go:11
 
 
 # ---------------------------------------------------------------------------
-# shape (mirrors capi.cpp levels_of / count_of: merkletree.go:31-64)
+# shape (mirrors csrc/context.hpp levels_of / count_of: merkletree.go:31-64)
 
 def levels_of(n: int) -> int:
     """Levels including the leaf level; build() always adds at least one."""
