@@ -39,6 +39,11 @@
  *     FindIndexTableEntry, record.Deserialize per table)
  *   Memtable.Flush over     core/memtable/memtable.go:93-116    nkv_sort_records_dev /
  *     skiplist.Write        core/skiplist/skiplist.go:62-120    nkv_sort_records
+ *   Memtable.Add / Find /   core/memtable/memtable.go:40-90     nkv_memtable_add_dev /
+ *     Count / ShouldFlush   core/skiplist/skiplist.go:52-120    nkv_memtable_find_dev /
+ *     (skiplist.Clear)                                            nkv_memtable_clear_dev
+ *   CoreEngine.get, memtable engine/coreeng/coreeng.go:79-86    nkv_memtable_find_dev (overlay)
+ *     step                                                        + nkv_lookup_values_dev
  *   record.New / ToBytes    core/record/record.go:49-60,175-187 nkv_encode_records_dev /
  *   wal.flushPartialBufferToSegment  core/wal/wal.go:199-232    nkv_encode_records
  *   (*HLL).Add / Estimate   ds/hll/hll.go:43-62, 75-92          nkv_hll_add[_records][_dev] /
@@ -76,7 +81,8 @@
  *         buffer of nkv_fill_splitmix64_dev, the merge's and the sort's d_out, d_index and
  *         d_summary of nkv_index_summary_dev, d_status and d_stage of
  *         nkv_lookup_dev, d_out of nkv_lookup_values_dev, d_out of
- *         nkv_encode_records_dev;
+ *         nkv_encode_records_dev, d_is_new of nkv_memtable_add_dev, d_status of
+ *         nkv_memtable_find_dev;
  *       digest arrays (d_nodes, nkv_table.nodes, d_roots and d_out entries of
  *         the group calls), 4-byte aligned: level starts inside a nodes buffer
  *         are multiples of 20 bytes, no more;
@@ -85,7 +91,7 @@
  *         d_out), 4-byte aligned;
  *       uint64_t arrays (d_rec_off, the frame's included, d_voff, d_vlen, d_stats,
  *         d_out_off, the encode's d_out_off included, d_out_src, d_hit,
- *         d_seg_first, d_seg_len), 8-byte aligned.
+ *         d_seg_first, d_seg_len, the memtable's d_state and d_index), 8-byte aligned.
  *     nkv_leaf_hash*_dev write level 0 only (20 n bytes); nkv_tree_reduce_dev
  *     leaves level 0 as given; d_bits is ((m + 31) / 32) * 4 bytes; the merge
  *     and the sort write out_len bytes and n_out entries; nkv_index_summary_dev writes
@@ -96,7 +102,11 @@
  *     and of d_crc; d_reg is 2^p bytes and d_table 4 K M bytes, both updated
  *     in place and never touched outside those extents; nkv_cms_query_dev
  *     writes n entries of d_out; nkv_frame_records_dev writes *n_out entries
- *     of d_rec_off, S + 1 of d_seg_first and S of d_seg_len.  Inputs are never
+ *     of d_rec_off, S + 1 of d_seg_first and S of d_seg_len;
+ *     nkv_memtable_add_dev writes n - n_done bytes of d_is_new, the four words
+ *     of d_state and, in place, the 8 slots bytes of d_index;
+ *     nkv_memtable_find_dev writes q entries of d_hit and d_status (with
+ *     overlay only those of the keys the memtable holds).  Inputs are never
  *     written: values, record streams, offset and length arrays, segment offsets, the merge's
  *     runs, the sort's log, the lookup's tables, filters and query keys, and the
  *     sketches' keys and the queried d_table are read in place
@@ -916,6 +926,99 @@ int nkv_lookup_dev(nkv_ctx *ctx, const nkv_lookup_table *tables, int T, const vo
 int nkv_lookup_values_dev(nkv_ctx *ctx, const nkv_lookup_table *tables, int T, const uint64_t *d_hit,
                           const uint8_t *d_status, uint64_t q, void *d_out, uint64_t out_cap,
                           uint64_t *d_out_off, uint64_t *out_len);
+
+/* ---- live memtable (core/memtable/memtable.go:40-90 over core/skiplist) ----
+ * Memtable.Add, Find, Count and ShouldFlush over a write log that stays on the
+ * device: the log nkv_encode_records_dev leaves (or a framed WAL segment) and
+ * nkv_sort_records_dev, the flush, takes.  A put batch, a read of it and the
+ * flush share one copy of the bytes.  There is no host-pointer form: the
+ * structure's state lives on the device.
+ *
+ * The index is caller-owned device memory: nkv_memtable_index_bytes(slots)
+ * bytes, 8-byte aligned, slots a power of two.  Its bytes are opaque and may
+ * differ from run to run; no answer derived from it does.  d_state is four
+ * uint64_t, 8-byte aligned: [0] Count, [1] memusage, [2] records indexed, [3]
+ * flush_at.
+ *
+ * What the reference's Add computes (tests/live_memtable_ref.py restates it
+ * statement by statement): the last write of a key replaces the whole record
+ * whatever its Timestamp or Status (skiplist.go:81), Add returns true exactly
+ * for the first write of a key since the clear, and memusage is the sum of
+ * TotalSize over those first writes -- an overwrite adds nothing, because
+ * skiplist.Write's oldNode aliases the node it has just updated
+ * (skiplist.go:80-81; DESIGN.md "Live memtable").  ShouldFlush (memtable.go:
+ * 70-73) is (strategy & NKV_FLUSH_BY_CAPACITY && Count == capacity) ||
+ * (strategy & NKV_FLUSH_BY_THRESHOLD && memusage >= threshold): equality for
+ * the capacity, so a memtable already above it never fires by capacity.
+ * Memtable.Remove (never called by the engine: Delete goes through put) and
+ * the LRU step of get are not provided. */
+#define NKV_FLUSH_BY_CAPACITY 1  /* coreconf.go:22 */
+#define NKV_FLUSH_BY_THRESHOLD 2 /* coreconf.go:23 */
+#define NKV_MEMTABLE_STATE_WORDS 4
+/* 8 * slots; 0 unless slots is a power of two in 2..2^32 */
+uint64_t nkv_memtable_index_bytes(uint64_t slots);
+/* skiplist.Clear + memusage = 0 (memtable.go:97-98): every slot empty, Count,
+ * memusage and the indexed count 0, flush_at UINT64_MAX.  Asynchronous.
+ * NKV_ERR_INVALID for a NULL pointer or a refused slots. */
+int nkv_memtable_clear_dev(nkv_ctx *ctx, void *d_index, uint64_t slots, uint64_t *d_state);
+/* Memtable.Add of records [n_done, n) of the log (d_log, log_len, d_rec_off as
+ * nkv_sort_records_dev takes them: dense, log_len the bytes up to the end of
+ * record n - 1), whose records [0, n_done) earlier calls indexed; the log's
+ * bytes and offsets up to n_done must be unchanged since (the caller's
+ * contract, not checked).  Asynchronous on the context's stream.
+ *
+ * After a successful add d_state[0] and [1] are what n sequential Adds since
+ * the clear leave, with no flush in between, [2] = n, and [3] = flush_at: the
+ * smallest arrival index i in [n_done, n) after whose Add ShouldFlush() is true
+ * under strategy / capacity / threshold, UINT64_MAX if there is none.  When it
+ * is set the caller does what the engine does (coreeng.go:214-218): flush
+ * records [0, flush_at], clear, add the rest as a new log.  d_is_new (nullable,
+ * n - n_done bytes at any address): d_is_new[i - n_done] = Add's return value
+ * for write i.  n == n_done writes flush_at = UINT64_MAX (and 0 to d_err) and
+ * nothing else.
+ *
+ * NKV_ERR_INVALID, with nothing launched: a NULL required pointer, n_done > n,
+ * n above 2^31 - 1, slots not a power of two in 2..2^32, n > slots / 2 (the
+ * load stays at or below one half, so every probe is finite), log_len / 30 < n.
+ * Device-side verdicts go to d_err (nullable, one uint32_t, need not be
+ * initialised; nonzero = the add was refused and the index, d_state and
+ * d_is_new are unchanged): bit 0 a record whose span does not hold or that
+ * does not end where the next starts (the last: at log_len), bit 1 an indexed
+ * count d_state[2] that is not n_done; bit 2 a probe that met no empty slot or
+ * a slot that names no record of this log -- the index was not cleared or is
+ * another log's, and may have been written.  With d_err NULL the call
+ * synchronizes and returns NKV_ERR_INVALID in those cases.
+ *
+ * Under NKV_TIMING_EVENTS the "leaf" interval is the validation, the insert
+ * and the new-write flags, the "reduce" interval the two scans, the flush
+ * point and the state update. */
+int nkv_memtable_add_dev(nkv_ctx *ctx, const void *d_log, uint64_t log_len, const uint64_t *d_rec_off,
+                         uint64_t n_done, uint64_t n, void *d_index, uint64_t slots, int strategy,
+                         uint64_t capacity, uint64_t threshold, uint64_t *d_state, uint8_t *d_is_new,
+                         uint32_t *d_err);
+/* Memtable.Find for q keys (queries as nkv_lookup_dev takes them: any
+ * alignment, the empty key and duplicates allowed) over the n indexed records.
+ * For a key the memtable holds, tombstones included (get then answers "not
+ * found" and stops, coreeng.go:80-85): d_hit[i] = ((uint64_t)table_id << 32) |
+ * arrival index of its latest write, d_status[i] = NKV_GET_LIVE or
+ * NKV_GET_TOMBSTONE (Status & 1).  For a key it does not hold: with overlay 0
+ * UINT64_MAX and NKV_GET_ABSENT; with overlay 1 both entries are left exactly
+ * as they were, so the call overlays nkv_lookup_dev's answers, and
+ * nkv_lookup_values_dev packs the Values of both with the log listed as table
+ * table_id (stream = d_log, rec_off, n, no filter).
+ *
+ * d_err (nullable, one uint32_t, need not be initialised) receives 1 if a
+ * probed record's key span reaches outside the log or a slot names no record
+ * below n, else 0; that probe counts as no match and nothing outside the log
+ * is read.  With d_err NULL the call synchronizes and returns NKV_ERR_INVALID
+ * in that case.  Also NKV_ERR_INVALID, with nothing launched: a NULL required
+ * pointer (d_log and d_rec_off may be NULL when n = 0), a refused slots, n or q
+ * above 2^31 - 1, table_id >= NKV_LOOKUP_MAX_TABLES.  q = 0 returns NKV_OK and
+ * writes nothing.  The call records no timing interval. */
+int nkv_memtable_find_dev(nkv_ctx *ctx, const void *d_log, uint64_t log_len, const uint64_t *d_rec_off,
+                          uint64_t n, const void *d_index, uint64_t slots, const void *d_keys,
+                          const uint64_t *d_koff, const uint64_t *d_klen, uint64_t q, uint32_t table_id,
+                          int overlay, uint64_t *d_hit, uint8_t *d_status, uint32_t *d_err);
 
 /* ---- several tables per call (compaction's runs, consecutive flushes) ----
  * One table of device-resident leaves, described for nkv_trees_dev /

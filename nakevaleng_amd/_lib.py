@@ -115,6 +115,9 @@ NKV_GET_ABSENT = 0
 NKV_GET_LIVE = 1
 NKV_GET_TOMBSTONE = 2
 NKV_HIT_NONE = 2**64 - 1  # d_hit of a key no table holds
+NKV_FLUSH_BY_CAPACITY = 1  # coreconf.go:22
+NKV_FLUSH_BY_THRESHOLD = 2  # coreconf.go:23
+NKV_MEMTABLE_STATE_WORDS = 4  # Count, memusage, records indexed, flush_at
 INDEX_WRITE_TILE = 16384  # csrc/index.hip kWriteTile: image bytes one writer workgroup owns
 _tabp = ctypes.POINTER(NkvTable)
 
@@ -206,6 +209,11 @@ SIGNATURES = {
     "nkv_lookup_dev": (_int, [_vp, ctypes.POINTER(NkvLookupTable), _int, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp]),
     "nkv_lookup_values_dev": (_int, [_vp, ctypes.POINTER(NkvLookupTable), _int, _vp, _vp, _u64, _vp, _u64, _vp,
                                      _u64p]),
+    "nkv_memtable_index_bytes": (_u64, [_u64]),
+    "nkv_memtable_clear_dev": (_int, [_vp, _vp, _u64, _vp]),
+    "nkv_memtable_add_dev": (_int, [_vp, _vp, _u64, _vp, _u64, _u64, _vp, _u64, _int, _u64, _u64, _vp, _vp, _vp]),
+    "nkv_memtable_find_dev": (_int, [_vp, _vp, _u64, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _u64, _u32, _int, _vp,
+                                     _vp, _vp]),
     "nkv_ctx_clock": (_int, [_vp, ctypes.POINTER(ctypes.c_double), _u64p]),
     "nkv_ctx_last_host_timing": (_int, [_vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float),
                                         ctypes.POINTER(ctypes.c_float)]),

@@ -26,6 +26,8 @@ boundaries found on the device (nkv_frame_records_dev), then flush_log's steps.
 The read side: upload_table() keeps a Data table (and its filter) resident, and
 get_many() answers a batch of keys over resident tables in search order
 (nkv_lookup_dev, nkv_lookup_values_dev), the disk part of the engine's get.
+With a memtable.Memtable it asks the live memtable first, as get does
+(nkv_memtable_find_dev laid over the tables' answers).
 """
 from __future__ import annotations
 
@@ -602,21 +604,33 @@ def upload_table(table: Table, filter=None, device=None) -> ResidentTable:
     return ResidentTable(dev_index, d_data, nbytes, d_off, n, d_bits, m, k, seed0)
 
 
-def get_many(tables: Sequence[ResidentTable], keys: Sequence[bytes], device=None, stages: bool = False):
+def get_many(tables: Sequence[ResidentTable], keys: Sequence[bytes], device=None, stages: bool = False,
+             memtable=None):
     """The disk part of the engine's get (coreeng.go:99-160) for a batch of
     keys over resident tables listed in search order (levels ascending, runs
     descending): per key the Value bytes of the first table that holds it, or
     None where no table does or that table holds a tombstone.  With `stages`
     the return is (values, the q x T array of NKV_STAGE codes, the q hits
-    (table << 32) | record index, NKV_HIT_NONE where absent)."""
+    (table << 32) | record index, NKV_HIT_NONE where absent).
+
+    With `memtable` (a memtable.Memtable) the steps of get run in order
+    (coreeng.go:79-160, without the LRU step): the table lookup as above
+    (skipped when `tables` is empty), the memtable's answers laid over it
+    (nkv_memtable_find_dev: a key the memtable holds is answered by its latest
+    write, a tombstone reading as not found), and one nkv_lookup_values_dev
+    over the tables plus the resident log, which a hit names as table
+    len(tables).  At most 31 tables then."""
     import ctypes
     import torch
     from . import _lib
     T, q = len(tables), len(keys)
-    if not 1 <= T <= _lib.NKV_LOOKUP_MAX_TABLES:
-        raise ValueError(f"get_many takes 1..{_lib.NKV_LOOKUP_MAX_TABLES} tables, got {T}")
-    dev_index = rank_device(device if device is not None else tables[0].device)
-    if any(t.device != dev_index for t in tables):
+    if memtable is None:
+        if not 1 <= T <= _lib.NKV_LOOKUP_MAX_TABLES:
+            raise ValueError(f"get_many takes 1..{_lib.NKV_LOOKUP_MAX_TABLES} tables, got {T}")
+    elif T > _lib.NKV_LOOKUP_MAX_TABLES - 1:
+        raise ValueError(f"get_many takes at most {_lib.NKV_LOOKUP_MAX_TABLES - 1} tables beside a memtable, got {T}")
+    dev_index = rank_device(device if device is not None else (tables[0].device if T else memtable.device))
+    if any(t.device != dev_index for t in tables) or (memtable is not None and memtable.device != dev_index):
         raise ValueError(f"get_many: every table must be resident on device {dev_index}")
     if q == 0:
         return ([], np.zeros((0, T), np.uint8), np.zeros(0, np.uint64)) if stages else []
@@ -636,13 +650,26 @@ def get_many(tables: Sequence[ResidentTable], keys: Sequence[bytes], device=None
     koff[1:] = np.cumsum(klen[:-1])
     d_keys, d_koff, d_klen = up(np.frombuffer(b"".join(keys) or b"\0", np.uint8)), up(koff), up(klen)
     d_hit, d_status, d_stage, d_err, d_out_off = u8(8 * q), u8(q), u8(q * T), u8(4), u8(8 * (q + 1))
-    tabs = (_lib.NkvLookupTable * T)(*[t.as_struct() for t in tables])
+    structs = [t.as_struct() for t in tables]
+    tabs = (_lib.NkvLookupTable * max(T, 1))(*structs)
+    with_mem = memtable is not None and memtable.n > 0  # an empty memtable holds no key
+    TV = T + 1 if with_mem else T  # the tables nkv_lookup_values_dev reads: the log is the last
+    vtabs = (_lib.NkvLookupTable * TV)(*(structs + [memtable.as_struct()])) if with_mem else tabs
     out_len = ctypes.c_uint64(0)
     stream = torch.cuda.current_stream(dev)
     with ctx.on_stream(stream.cuda_stream):
-        _lib.check(L.nkv_lookup_dev(ctx.h, tabs, T, d_keys.data_ptr(), d_koff.data_ptr(), d_klen.data_ptr(), q,
-                                    d_hit.data_ptr(), d_status.data_ptr(), d_stage.data_ptr(), d_err.data_ptr()),
-                   "point lookup")
+        if T:
+            _lib.check(L.nkv_lookup_dev(ctx.h, tabs, T, d_keys.data_ptr(), d_koff.data_ptr(), d_klen.data_ptr(), q,
+                                        d_hit.data_ptr(), d_status.data_ptr(), d_stage.data_ptr(), d_err.data_ptr()),
+                       "point lookup")
+        else:
+            d_hit.fill_(0xFF)  # no table: every key absent until the memtable answers
+        if with_mem:
+            memtable.find_dev(d_keys, d_koff, d_klen, q, d_hit, d_status, table_id=T, overlay=True)
+        if TV == 0:
+            return ([None] * q, np.zeros((q, 0), np.uint8), np.full(q, _lib.NKV_HIT_NONE, np.uint64)) if stages \
+                else [None] * q
+        tabs, T_stage, T = vtabs, T, TV
         _lib.check(L.nkv_lookup_values_dev(ctx.h, tabs, T, d_hit.data_ptr(), d_status.data_ptr(), q, None, 0, None,
                                            ctypes.byref(out_len)), "point lookup, Value sizes")
         if int(d_err.cpu().numpy().view(np.uint32)[0]):
@@ -658,7 +685,7 @@ def get_many(tables: Sequence[ResidentTable], keys: Sequence[bytes], device=None
     values = [packed[off[i]:off[i + 1]] if status[i] == _lib.NKV_GET_LIVE else None for i in range(q)]
     if not stages:
         return values
-    return (values, d_stage.cpu().numpy()[:q * T].reshape(q, T).copy(),
+    return (values, d_stage.cpu().numpy()[:q * T_stage].reshape(q, T_stage).copy(),
             d_hit.cpu().numpy().view(np.uint64)[:q].copy())
 
 
