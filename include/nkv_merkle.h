@@ -80,7 +80,7 @@
  *       byte strings, at any address: d_img, nkv_bloom_query_dev's d_out, the
  *         buffer of nkv_fill_splitmix64_dev, the merge's and the sort's d_out, d_index and
  *         d_summary of nkv_index_summary_dev, d_status and d_stage of
- *         nkv_lookup_dev, d_out of nkv_lookup_values_dev, d_out of
+ *         nkv_lookup_dev and nkv_locate_dev, d_out of nkv_lookup_values_dev, d_out of
  *         nkv_encode_records_dev, d_is_new of nkv_memtable_add_dev, d_status of
  *         nkv_memtable_find_dev;
  *       digest arrays (d_nodes, nkv_table.nodes, d_roots and d_out entries of
@@ -91,7 +91,8 @@
  *         d_out), 4-byte aligned;
  *       uint64_t arrays (d_rec_off, the frame's included, d_voff, d_vlen, d_stats,
  *         d_out_off, the encode's d_out_off included, d_out_src, d_hit,
- *         d_seg_first, d_seg_len, the memtable's d_state and d_index), 8-byte aligned.
+ *         d_seg_first, d_seg_len, the memtable's d_state and d_index, d_ent_off,
+ *         d_data_off), 8-byte aligned.
  *     nkv_leaf_hash*_dev write level 0 only (20 n bytes); nkv_tree_reduce_dev
  *     leaves level 0 as given; d_bits is ((m + 31) / 32) * 4 bytes; the merge
  *     and the sort write out_len bytes and n_out entries; nkv_index_summary_dev writes
@@ -106,9 +107,14 @@
  *     nkv_memtable_add_dev writes n - n_done bytes of d_is_new, the four words
  *     of d_state and, in place, the 8 slots bytes of d_index;
  *     nkv_memtable_find_dev writes q entries of d_hit and d_status (with
- *     overlay only those of the keys the memtable holds).  Inputs are never
+ *     overlay only those of the keys the memtable holds); nkv_index_open_dev
+ *     writes *n_out entries of d_ent_off, and none for a refused pair;
+ *     nkv_locate_dev writes q entries of d_hit, d_data_off and d_status (with
+ *     overlay only those whose status was ABSENT) and q T bytes of d_stage.
+ *     Inputs are never
  *     written: values, record streams, offset and length arrays, segment offsets, the merge's
- *     runs, the sort's log, the lookup's tables, filters and query keys, and the
+ *     runs, the sort's log, the lookup's tables, filters and query keys, the
+ *     Index and Summary images of nkv_index_open_dev and nkv_locate_dev, and the
  *     sketches' keys and the queried d_table are read in place
  *     (at any alignment where they are bytes).
  *   - Offsets, strides and stream lengths are full 64-bit quantities: the
@@ -276,6 +282,15 @@ int nkv_ctx_sync(nkv_ctx *ctx);
                                    per 64 stream bytes for the marks plus about 17 per candidate
                                    start; 0 (default) = auto: min(2 * stream_len, a quarter of the
                                    free device memory) */
+#define NKV_OPT_INDEX_OPEN_PATH 24 /* nkv_index_open_dev, the Summary chain: 0 (default) = auto: the
+                                      one-lane walk for a payload below 16 KiB, else chunked; 1 = one
+                                      lane follows the payload; 2 = chunked: one lane per
+                                      NKV_OPT_INDEX_OPEN_CHUNK payload bytes starts at the first
+                                      position of its chunk that passes the link test, the host
+                                      stitches the lanes, and any mismatch takes the walk.  Every
+                                      value gives the same bytes */
+#define NKV_OPT_INDEX_OPEN_CHUNK 25 /* payload bytes per lane of the chunked Summary walk: a multiple
+                                       of 16 in 16..2^24; 0 (default) = 4096 */
 int nkv_ctx_set_option(nkv_ctx *ctx, int key, int64_t value);
 /* Which path the latest host-buffer tree call, or the latest frame call, of the context took */
 #define NKV_PATH_GRID 0  /* copies + leaf kernel + per-level reduce launches */
@@ -926,6 +941,103 @@ int nkv_lookup_dev(nkv_ctx *ctx, const nkv_lookup_table *tables, int T, const vo
 int nkv_lookup_values_dev(nkv_ctx *ctx, const nkv_lookup_table *tables, int T, const uint64_t *d_hit,
                           const uint8_t *d_status, uint64_t q, void *d_out, uint64_t out_cap,
                           uint64_t *d_out_off, uint64_t *out_len);
+
+/* ---- index lookup (the same get, over tables whose Data file stays on disk) ----
+ * nkv_lookup_dev answers over tables whose whole Data stream is resident.  The
+ * engine's get never touches Data until Filter, Summary and Index have named
+ * one record offset, and a table's Index is about a hundredth of its Data: a
+ * key directory on the device -- the filter words and the Index of every table
+ * -- takes a batch of keys and returns, per key, the answering table and the
+ * record's Data-file offset; the host then does one pread per hit.
+ *
+ * Both files are chains of entries KeySize u64 | Offset i64 | Key with no
+ * offsets beside them (the Summary behind MinKeySize u64 | MaxKeySize u64 |
+ * Payload u64 | MinKey | MaxKey), so a table is opened first.  Call an
+ * Index/Summary pair canonical when (n Index entries, s Summary entries)
+ *   1. the Summary holds its 24-byte header, MinKey, MaxKey and Payload bytes
+ *      (bytes behind them are ignored, as the reference ignores them);
+ *   2. the payload is a whole chain of s >= 1 entries ending exactly at Payload;
+ *   3. the Index is a whole chain of n >= 1 entries ending exactly at index_len;
+ *   4. every Summary entry's Offset is the byte offset of an Index entry with
+ *      the same KeySize and Key, the first names Index entry 0, the last names
+ *      entry n - 1, and the named entries strictly ascend;
+ *   5. the Index keys strictly increase under bytes.Compare;
+ *   6. MinKey = K_0 and MaxKey = K_(n-1).
+ * An entry whose KeySize reaches past the end of its image ends its chain
+ * there (the reference's Read reports EOF).  Everything makeIndexAndSummary
+ * writes from a flushed or merged table is canonical at any page size, and so
+ * is any other partition into pages.  On a canonical pair FindSummaryTableEntry
+ * and FindIndexTableEntry reduce to: SUMMARY exactly when key < K_0 or key >
+ * K_(n-1); else, with j the lower bound of the key among the Index keys, FOUND
+ * with entry j's stored Offset if K_j equals the key and that stored Offset is
+ * not -1 (coreeng.go:138 tests the stored field), INDEX otherwise
+ * (tests/index_open_ref.py holds this to the literal restatement).  A pair that
+ * is not canonical is refused by the open and never reaches the locate: the
+ * reference's answer on it depends on its scan order, and its one-key host
+ * reader remains the way to serve it. */
+#define NKV_INDEX_BAD_HEADER 1         /* condition 1 */
+#define NKV_INDEX_BAD_SUMMARY_CHAIN 2  /* condition 2 */
+#define NKV_INDEX_BAD_INDEX_CHAIN 4    /* condition 3 */
+#define NKV_INDEX_BAD_LINK 8           /* condition 4 */
+#define NKV_INDEX_BAD_ORDER 16         /* condition 5 */
+#define NKV_INDEX_BAD_RANGE 32         /* condition 6 */
+/* Parse and validate one pair.  Synchronous: it hands n to the host.  Both
+ * images on the context's device, at any byte alignment; d_ent_off (8-byte
+ * aligned, ent_cap entries) receives the n byte offsets of the Index entries,
+ * ascending -- exactly n entries, and only when the verdict is 0.  n_out, s_out
+ * and verdict are host pointers.  *verdict = 0 for a canonical pair, else a bit
+ * mask whose lowest set bit names the first failed condition (later ones are
+ * not evaluated); a refused pair returns NKV_OK with *n_out = *s_out = 0.  With
+ * d_ent_off NULL the call is a size query: n, s and the verdict.  ent_cap < n
+ * returns NKV_ERR_INVALID with n still reported; index_len / 16 entries are
+ * always enough.  NKV_ERR_INVALID, with nothing launched: a NULL context, image
+ * or host pointer, index_len or summary_len of 0; and n or s above 2^31 - 1.
+ * Nothing outside the two images is read, whatever their bytes say.
+ *
+ * The Summary chain is followed by one lane or in chunks
+ * (NKV_OPT_INDEX_OPEN_PATH); the Index chain by one lane per Summary page, so a
+ * table written as one giant page parses at the one-lane rate.  Scratch is the
+ * context's: about index_len / 2 + 2 * Payload bytes. */
+int nkv_index_open_dev(nkv_ctx *ctx, const void *d_index, uint64_t index_len, const void *d_summary,
+                       uint64_t summary_len, uint64_t *d_ent_off, uint64_t ent_cap, uint64_t *n_out,
+                       uint64_t *s_out, uint32_t *verdict);
+
+typedef struct nkv_index_table { /* all pointers on the context's device */
+    const void *index;       /* the Index file's bytes, any alignment */
+    uint64_t index_len;
+    const uint64_t *ent_off; /* n entry offsets, from a verdict-0 nkv_index_open_dev */
+    uint64_t n;              /* >= 1 */
+    const void *bits;        /* filter words, as nkv_lookup_table */
+    uint32_t m, k, seed0;
+} nkv_index_table;
+#define NKV_GET_LOCATED 3 /* found in an Index; Status is in the Data record on disk */
+
+/* Asynchronous on the context's stream.  Queries as nkv_lookup_dev takes them.
+ * Per table, in the order given: the filter test, the range test against
+ * entries 0 and n - 1, a lower bound over ent_off with each probed key read in
+ * place.  For the first table whose search ends FOUND: d_hit[i] =
+ * ((uint64_t)(table_base + t) << 32) | entry index, d_data_off[i] = the entry's
+ * stored Offset, d_status[i] = NKV_GET_LOCATED; when none does: UINT64_MAX, -1
+ * and NKV_GET_ABSENT.  d_stage (nullable, q * T bytes) holds the NKV_STAGE
+ * codes; a stored Offset of -1 ends that table's search at INDEX.
+ *
+ * With overlay 1 a query whose d_status[i] is not NKV_GET_ABSENT is left
+ * exactly as it was in d_hit, d_data_off and d_status, and its stage row is all
+ * NOT_SEARCHED: the call lays the disk tables under the answers of
+ * nkv_lookup_dev and nkv_memtable_find_dev (d_data_off is then read only where
+ * the status is LOCATED).  The search order is the caller's: every resident
+ * table ahead of every Index-only one.
+ *
+ * d_err as in nkv_lookup_dev: 1 if a probed entry reaches outside its image
+ * (that probe counts as no match); with d_err NULL the call synchronizes and
+ * returns NKV_ERR_INVALID in that case.  Also NKV_ERR_INVALID, with nothing
+ * launched: T outside 1..NKV_LOOKUP_MAX_TABLES, table_base + T above 65536, a
+ * table with n = 0 or a NULL index or ent_off, a filter with k > 0 and m = 0, n
+ * or q above 2^31 - 1, a NULL required pointer.  q = 0 writes nothing. */
+int nkv_locate_dev(nkv_ctx *ctx, const nkv_index_table *tables, int T, uint32_t table_base,
+                   const void *d_keys, const uint64_t *d_koff, const uint64_t *d_klen, uint64_t q,
+                   int overlay, uint64_t *d_hit, int64_t *d_data_off, uint8_t *d_status,
+                   uint8_t *d_stage, uint32_t *d_err);
 
 /* ---- live memtable (core/memtable/memtable.go:40-90 over core/skiplist) ----
  * Memtable.Add, Find, Count and ShouldFlush over a write log that stays on the

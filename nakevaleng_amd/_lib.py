@@ -41,6 +41,8 @@ NKV_OPT_SERVICE_MAILBOX = 20
 NKV_OPT_SKETCH_PATH = 21  # 0 auto, 1 direct global atomics, 2 workgroup-private copies in LDS
 NKV_OPT_FRAME_PATH = 22  # 0 auto, 1 walk (one lane per segment), 2 speculative (mark, successor, doubling)
 NKV_OPT_FRAME_BUDGET = 23  # bytes of scratch a speculative frame call may use (0 = auto)
+NKV_OPT_INDEX_OPEN_PATH = 24  # nkv_index_open_dev's Summary chain: 0 auto, 1 one-lane walk, 2 chunked
+NKV_OPT_INDEX_OPEN_CHUNK = 25  # payload bytes per lane of the chunked walk (0 = 4096)
 NKV_FRAME_STRICT = 1
 NKV_HLL_MIN_PRECISION = 4
 NKV_HLL_MAX_PRECISION = 16
@@ -96,6 +98,12 @@ class NkvLookupTable(ctypes.Structure):
                 ("m", ctypes.c_uint32), ("k", ctypes.c_uint32), ("seed0", ctypes.c_uint32)]
 
 
+class NkvIndexTable(ctypes.Structure):
+    """struct nkv_index_table: one opened Index of nkv_locate_dev (bits None = no filter)."""
+    _fields_ = [("index", _vp), ("index_len", _u64), ("ent_off", _vp), ("n", _u64), ("bits", _vp),
+                ("m", ctypes.c_uint32), ("k", ctypes.c_uint32), ("seed0", ctypes.c_uint32)]
+
+
 class NkvPuts(ctypes.Structure):
     """struct nkv_puts: a batch of (key, value) pairs for nkv_encode_records[_dev]
     (ts None = ts_all in every record; status / type None = 0)."""
@@ -114,7 +122,16 @@ NKV_STAGE_FOUND = 4
 NKV_GET_ABSENT = 0
 NKV_GET_LIVE = 1
 NKV_GET_TOMBSTONE = 2
+NKV_GET_LOCATED = 3  # nkv_locate_dev: found in an Index, the record is in the Data file
 NKV_HIT_NONE = 2**64 - 1  # d_hit of a key no table holds
+NKV_INDEX_BAD_HEADER = 1
+NKV_INDEX_BAD_SUMMARY_CHAIN = 2
+NKV_INDEX_BAD_INDEX_CHAIN = 4
+NKV_INDEX_BAD_LINK = 8
+NKV_INDEX_BAD_ORDER = 16
+NKV_INDEX_BAD_RANGE = 32
+INDEX_VERDICTS = {1: "BAD_HEADER", 2: "BAD_SUMMARY_CHAIN", 4: "BAD_INDEX_CHAIN", 8: "BAD_LINK", 16: "BAD_ORDER",
+                  32: "BAD_RANGE"}
 NKV_FLUSH_BY_CAPACITY = 1  # coreconf.go:22
 NKV_FLUSH_BY_THRESHOLD = 2  # coreconf.go:23
 NKV_MEMTABLE_STATE_WORDS = 4  # Count, memusage, records indexed, flush_at
@@ -209,6 +226,9 @@ SIGNATURES = {
     "nkv_lookup_dev": (_int, [_vp, ctypes.POINTER(NkvLookupTable), _int, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp]),
     "nkv_lookup_values_dev": (_int, [_vp, ctypes.POINTER(NkvLookupTable), _int, _vp, _vp, _u64, _vp, _u64, _vp,
                                      _u64p]),
+    "nkv_index_open_dev": (_int, [_vp, _vp, _u64, _vp, _u64, _vp, _u64, _u64p, _u64p, ctypes.POINTER(_u32)]),
+    "nkv_locate_dev": (_int, [_vp, ctypes.POINTER(NkvIndexTable), _int, _u32, _vp, _vp, _vp, _u64, _int, _vp, _vp,
+                              _vp, _vp, _vp]),
     "nkv_memtable_index_bytes": (_u64, [_u64]),
     "nkv_memtable_clear_dev": (_int, [_vp, _vp, _u64, _vp]),
     "nkv_memtable_add_dev": (_int, [_vp, _vp, _u64, _vp, _u64, _u64, _vp, _u64, _int, _u64, _u64, _vp, _vp, _vp]),

@@ -19,7 +19,7 @@ ROOT = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
 SO = os.path.join(PKG, "libnkvmerkle.so")
 SOURCES = ["leaf.hip", "reduce.hip", "small_tree.hip", "plan.hip", "crc.hip", "bloom.hip", "merge.hip",
-           "memtable.hip", "memindex.hip", "index.hip", "lookup.hip", "encode.hip", "sketch.hip", "frame.hip",
+           "memtable.hip", "memindex.hip", "index.hip", "lookup.hip", "locate.hip", "encode.hip", "sketch.hip", "frame.hip",
            "context.cpp", "stage.cpp", "tree.cpp", "small_host.cpp",
            "group.cpp", "host_stage.cpp"]
 HEADERS = ["internal.hpp", "context.hpp", "sha1_dev.hpp", "sha1_feed_dev.hpp", "tree_dev.hpp", "host_stage.hpp",

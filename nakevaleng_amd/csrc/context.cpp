@@ -263,6 +263,7 @@ int nkv_ctx_set_option(nkv_ctx* c, int key, int64_t value) try {
             case NKV_OPT_BLOOM_PATH: return {&c->bloom_path, 0, 2};
             case NKV_OPT_SKETCH_PATH: return {&c->sketch_path, 0, 2};
             case NKV_OPT_FRAME_PATH: return {&c->frame_path, 0, 2};
+            case NKV_OPT_INDEX_OPEN_PATH: return {&c->index_open_path, 0, 2};
             case NKV_OPT_HOST_THREADS: return {&c->stage.want_threads, 0, 256};
             case NKV_OPT_RECORDS_FUSED: return {&c->records_fused, 0, 1};
             case NKV_OPT_QUEUE_WAVES: return {&c->queue_waves, 1, 3};  // 12 KiB ring per wave: <= 13 per CU
@@ -294,6 +295,10 @@ int nkv_ctx_set_option(nkv_ctx* c, int key, int64_t value) try {
         case NKV_OPT_FRAME_BUDGET:
             if (value < 0) return NKV_ERR_INVALID;
             c->frame_budget = uint64_t(value);
+            return NKV_OK;
+        case NKV_OPT_INDEX_OPEN_CHUNK:
+            if (value != 0 && (value < 16 || value > (int64_t(1) << 24) || (value & 15))) return NKV_ERR_INVALID;
+            c->index_open_chunk = int(value);
             return NKV_OK;
         case NKV_OPT_STAGE_CHUNK:
             if (value < 4096 || value > (int64_t(1) << 32) || (value & 4095)) return NKV_ERR_INVALID;

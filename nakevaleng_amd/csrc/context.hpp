@@ -213,6 +213,8 @@ struct nkv_ctx {
     int sketch_path = 0;    // NKV_OPT_SKETCH_PATH
     int frame_path = 0;     // NKV_OPT_FRAME_PATH
     uint64_t frame_budget = 0;  // NKV_OPT_FRAME_BUDGET (0 = auto)
+    int index_open_path = 0;   // NKV_OPT_INDEX_OPEN_PATH
+    int index_open_chunk = 0;  // NKV_OPT_INDEX_OPEN_CHUNK (0 = the default)
     int crc_load = 0;       // NKV_OPT_CRC_LOAD
     int records_fused = 1;  // NKV_OPT_RECORDS_FUSED
     int table_lanes = 2;    // NKV_OPT_TABLE_LANES

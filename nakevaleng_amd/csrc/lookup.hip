@@ -73,30 +73,11 @@ __device__ __forceinline__ int probe(const Query& Q, const uint8_t* __restrict__
     return cmp_prefixed(Q.pfx, Q.len, Q.key + 8, key_prefix(rk, ks), ks, rk + 8);
 }
 
-// Filter.Query (bloomfilter.go:93-111): every one of the k bits set.
-__device__ __forceinline__ bool filter_passes(const Query& Q, const uint32_t* __restrict__ bits, uint32_t m, uint64_t M,
-                                              uint32_t k, uint32_t seed0) {
-    bool hit = true;
-    for (uint32_t j0 = 0; j0 < k && hit; j0 += kBloomMaxK) {
-        const int nk = int(min(k - j0, uint32_t(kBloomMaxK)));
-        uint32_t h[kBloomMaxK];
-        mm_states(Q.key, Q.len, seed0 + j0, nk, h);
-#pragma unroll
-        for (int j = 0; j < kBloomMaxK; ++j) {
-            if (j < nk) {
-                const uint32_t idx = fastmod_u32(mm_fmix(h[j] ^ uint32_t(Q.len)), M, m);
-                hit = hit && ((bits[idx >> 5] >> (idx & 31u)) & 1u);
-            }
-        }
-    }
-    return hit;
-}
-
 // One table's search: the stage it ends at and, when FOUND, the record index.
 // A bad probe ends the search at INDEX (no equal key) and raises *bad.
 __device__ __forceinline__ uint32_t search(const Tables& R, int t, const Query& Q, uint64_t* found, bool* bad) {
     const uint32_t* bits = R.bits[t];
-    if (bits && !filter_passes(Q, bits, R.m[t], R.M[t], R.k[t], R.seed[t])) return NKV_STAGE_FILTER;
+    if (bits && !filter_query(Q.key, Q.len, bits, R.m[t], R.M[t], R.k[t], R.seed[t])) return NKV_STAGE_FILTER;
     const uint8_t* s = R.stream[t];
     const uint64_t L = R.len[t];
     const uint64_t* off = R.off[t];

@@ -1,6 +1,6 @@
 // murmur_dev.hpp -- MurmurHash3_x86_32 (spaolacci/murmur3 v1.1.0 Sum32) on the
 // device, several seeds at once, shared by the filter build (bloom.hip) and the
-// point lookup's filter test (lookup.hip).
+// filter test of the point lookups (lookup.hip, locate.hip).
 //
 // The key's 4-byte little-endian blocks come from aligned dword loads funnelled
 // by the key's byte offset (v_alignbyte), so any alignment works and no load
@@ -69,6 +69,26 @@ __device__ __forceinline__ void mm_states(const uint8_t* key, uint64_t len, uint
         for (int j = 0; j < kBloomMaxK; ++j)
             if (j < nk) h[j] ^= k;
     }
+}
+
+// Filter.Query (bloomfilter.go:93-111) of one key: every one of the k bits set.
+// M = fastmod_magic(m).
+__device__ __forceinline__ bool filter_query(const uint8_t* key, uint64_t len, const uint32_t* __restrict__ bits,
+                                             uint32_t m, uint64_t M, uint32_t k, uint32_t seed0) {
+    bool hit = true;
+    for (uint32_t j0 = 0; j0 < k && hit; j0 += kBloomMaxK) {
+        const int nk = int(min(k - j0, uint32_t(kBloomMaxK)));
+        uint32_t h[kBloomMaxK];
+        mm_states(key, len, seed0 + j0, nk, h);
+#pragma unroll
+        for (int j = 0; j < kBloomMaxK; ++j) {
+            if (j < nk) {
+                const uint32_t idx = fastmod_u32(mm_fmix(h[j] ^ uint32_t(len)), M, m);
+                hit = hit && ((bits[idx >> 5] >> (idx & 31u)) & 1u);
+            }
+        }
+    }
+    return hit;
 }
 
 }  // namespace nkv

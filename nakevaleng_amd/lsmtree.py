@@ -28,6 +28,12 @@ get_many() answers a batch of keys over resident tables in search order
 (nkv_lookup_dev, nkv_lookup_values_dev), the disk part of the engine's get.
 With a memtable.Memtable it asks the live memtable first, as get does
 (nkv_memtable_find_dev laid over the tables' answers).
+
+Tables whose Data file stays on disk keep only their Index and filter on the
+device (sstable.open_index): locate_many() names, per key, the answering table
+and the record's Data-file offset (nkv_locate_dev), and get_many_on_disk() lays
+those tables under the memtable's and the resident tables' answers and reads
+one record per hit from the Data files.
 """
 from __future__ import annotations
 
@@ -605,7 +611,7 @@ def upload_table(table: Table, filter=None, device=None) -> ResidentTable:
 
 
 def get_many(tables: Sequence[ResidentTable], keys: Sequence[bytes], device=None, stages: bool = False,
-             memtable=None):
+             memtable=None, _indexed=(), _data_files=()):
     """The disk part of the engine's get (coreeng.go:99-160) for a batch of
     keys over resident tables listed in search order (levels ascending, runs
     descending): per key the Value bytes of the first table that holds it, or
@@ -619,18 +625,27 @@ def get_many(tables: Sequence[ResidentTable], keys: Sequence[bytes], device=None
     (nkv_memtable_find_dev: a key the memtable holds is answered by its latest
     write, a tombstone reading as not found), and one nkv_lookup_values_dev
     over the tables plus the resident log, which a hit names as table
-    len(tables).  At most 31 tables then."""
+    len(tables).  At most 31 tables then.
+
+    _indexed / _data_files are get_many_on_disk's: Index-only tables searched
+    behind everything resident, and their Data files."""
     import ctypes
     import torch
     from . import _lib
     T, q = len(tables), len(keys)
-    if memtable is None:
+    if _indexed:
+        if T + (memtable is not None) > _lib.NKV_LOOKUP_MAX_TABLES:
+            raise ValueError(f"get_many_on_disk takes at most {_lib.NKV_LOOKUP_MAX_TABLES} resident tables, "
+                             f"the memtable included, got {T + (memtable is not None)}")
+    elif memtable is None:
         if not 1 <= T <= _lib.NKV_LOOKUP_MAX_TABLES:
             raise ValueError(f"get_many takes 1..{_lib.NKV_LOOKUP_MAX_TABLES} tables, got {T}")
     elif T > _lib.NKV_LOOKUP_MAX_TABLES - 1:
         raise ValueError(f"get_many takes at most {_lib.NKV_LOOKUP_MAX_TABLES - 1} tables beside a memtable, got {T}")
-    dev_index = rank_device(device if device is not None else (tables[0].device if T else memtable.device))
-    if any(t.device != dev_index for t in tables) or (memtable is not None and memtable.device != dev_index):
+    first = tables[0] if T else (memtable if memtable is not None else _indexed[0])
+    dev_index = rank_device(device if device is not None else first.device)
+    if any(t.device != dev_index for t in list(tables) + list(_indexed)) or \
+            (memtable is not None and memtable.device != dev_index):
         raise ValueError(f"get_many: every table must be resident on device {dev_index}")
     if q == 0:
         return ([], np.zeros((0, T), np.uint8), np.zeros(0, np.uint64)) if stages else []
@@ -666,7 +681,12 @@ def get_many(tables: Sequence[ResidentTable], keys: Sequence[bytes], device=None
             d_hit.fill_(0xFF)  # no table: every key absent until the memtable answers
         if with_mem:
             memtable.find_dev(d_keys, d_koff, d_klen, q, d_hit, d_status, table_id=T, overlay=True)
+        if _indexed:  # the disk tables under every resident answer, named TV, TV + 1, ..
+            located = _locate_under(ctx, L, _indexed, TV, d_keys, d_koff, d_klen, q, d_hit, d_status, u8)
         if TV == 0:
+            if _indexed:
+                stream.synchronize()
+                return read_located(_data_files, _located_of(located, d_hit, d_status, q, 0), keys)
             return ([None] * q, np.zeros((q, 0), np.uint8), np.full(q, _lib.NKV_HIT_NONE, np.uint64)) if stages \
                 else [None] * q
         tabs, T_stage, T = vtabs, T, TV
@@ -683,10 +703,157 @@ def get_many(tables: Sequence[ResidentTable], keys: Sequence[bytes], device=None
     off = d_out_off.cpu().numpy().view(np.uint64)[:q + 1].tolist()
     packed = d_out.cpu().numpy()[:out_len.value].tobytes()
     values = [packed[off[i]:off[i + 1]] if status[i] == _lib.NKV_GET_LIVE else None for i in range(q)]
+    if _indexed:
+        on_disk = read_located(_data_files, _located_of(located, d_hit, d_status, q, T), keys)
+        return [v if status[i] != _lib.NKV_GET_LOCATED else on_disk[i] for i, v in enumerate(values)]
     if not stages:
         return values
     return (values, d_stage.cpu().numpy()[:q * T_stage].reshape(q, T_stage).copy(),
             d_hit.cpu().numpy().view(np.uint64)[:q].copy())
+
+
+# ---------------------------------------------------------------------------
+# tables whose Data file stays on disk (nkv_locate_dev over sstable.IndexedTable)
+
+def _locate_under(ctx, L, indexed, base, d_keys, d_koff, d_klen, q, d_hit, d_status, u8):
+    """nkv_locate_dev with overlay over the answers in d_hit / d_status, the
+    Index-only tables named base, base + 1, ..; in chunks of
+    NKV_LOOKUP_MAX_TABLES, each laid under the ones before.  Returns the
+    d_data_off tensor."""
+    from . import _lib
+    d_data_off = u8(8 * q)
+    for t0 in range(0, len(indexed), _lib.NKV_LOOKUP_MAX_TABLES):
+        part = indexed[t0:t0 + _lib.NKV_LOOKUP_MAX_TABLES]
+        tabs = (_lib.NkvIndexTable * len(part))(*[t.as_struct() for t in part])
+        _lib.check(L.nkv_locate_dev(ctx.h, tabs, len(part), base + t0, d_keys.data_ptr(), d_koff.data_ptr(),
+                                    d_klen.data_ptr(), q, 1, d_hit.data_ptr(), d_data_off.data_ptr(),
+                                    d_status.data_ptr(), None, None), "index lookup")
+    return d_data_off
+
+
+def _located_of(d_data_off, d_hit, d_status, q, base):
+    """Per query (Index-only table, Data offset) of a LOCATED answer, else None."""
+    from . import _lib
+    status = d_status.cpu().numpy()[:q]
+    hit = d_hit.cpu().numpy().view(np.uint64)[:q]
+    off = d_data_off.cpu().numpy().view(np.int64)[:q]
+    return [(int(hit[i] >> np.uint64(32)) - base, int(off[i])) if status[i] == _lib.NKV_GET_LOCATED else None
+            for i in range(q)]
+
+
+def locate_many(tables, keys: Sequence[bytes], stages: bool = False, base: int = 0):
+    """FindSummaryTableEntry and FindIndexTableEntry for a batch of keys over
+    Index-only tables (sstable.IndexedTable, at most 32) in search order: per
+    key (table, Data-file offset) of the first table whose Index holds it with a
+    stored Offset other than -1, or None.  `base` is added to the table numbers.
+    With `stages` the return is (that list, the q x T array of NKV_STAGE codes,
+    the q hits ((base + table) << 32) | entry index, NKV_HIT_NONE where absent)."""
+    import torch
+    from . import _lib
+    T, q = len(tables), len(keys)
+    if not 1 <= T <= _lib.NKV_LOOKUP_MAX_TABLES:
+        raise ValueError(f"locate_many takes 1..{_lib.NKV_LOOKUP_MAX_TABLES} tables, got {T}")
+    dev_index = tables[0].device
+    if any(t.device != dev_index for t in tables):
+        raise ValueError(f"locate_many: every table must be open on device {dev_index}")
+    if q == 0:
+        return ([], np.zeros((0, T), np.uint8), np.zeros(0, np.uint64)) if stages else []
+    ctx = _lib.default_context(dev_index)
+    dev = torch.device("cuda", dev_index)
+
+    def up(a):
+        return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).copy()).to(dev)
+
+    def u8(nbytes):
+        return torch.zeros(max(int(nbytes), 16), dtype=torch.uint8, device=dev)
+
+    keys = [bytes(k) for k in keys]
+    klen = np.fromiter((len(k) for k in keys), dtype=np.uint64, count=q)
+    koff = np.zeros(q, np.uint64)
+    koff[1:] = np.cumsum(klen[:-1])
+    d_keys, d_koff, d_klen = up(np.frombuffer(b"".join(keys) or b"\0", np.uint8)), up(koff), up(klen)
+    d_hit, d_off, d_status, d_stage, d_err = u8(8 * q), u8(8 * q), u8(q), u8(q * T), u8(4)
+    tabs = (_lib.NkvIndexTable * T)(*[t.as_struct() for t in tables])
+    stream = torch.cuda.current_stream(dev)
+    with ctx.on_stream(stream.cuda_stream):
+        _lib.check(_lib.lib().nkv_locate_dev(ctx.h, tabs, T, base, d_keys.data_ptr(), d_koff.data_ptr(),
+                                             d_klen.data_ptr(), q, 0, d_hit.data_ptr(), d_off.data_ptr(),
+                                             d_status.data_ptr(), d_stage.data_ptr(), d_err.data_ptr()),
+                   "index lookup")
+        stream.synchronize()
+    if int(d_err.cpu().numpy().view(np.uint32)[0]):
+        raise _lib.NkvError(_lib.NKV_ERR_INVALID, "index lookup: an entry reaches outside its Index")
+    out = _located_of(d_off, d_hit, d_status, q, 0)
+    if not stages:
+        return out
+    return out, d_stage.cpu().numpy()[:q * T].reshape(q, T).copy(), d_hit.cpu().numpy().view(np.uint64)[:q].copy()
+
+
+def read_located(data_files, located, keys=None, read_hint: int = 8192):
+    """The host half of get_many_on_disk.  located[i] is (table, Data offset)
+    or None; data_files[table] is that table's Data file (a path or an open
+    file descriptor).  Per hit: one os.pread of read_hint bytes at the offset
+    (a second one for the rest of a longer record), then record.Deserialize's
+    work (record.go:119-172): the 30-byte header, Key and Value, and the stored
+    Crc checked -- a mismatch raises ValueError where the reference panics.
+    Returns the Value, or None for a miss or a tombstone.  With `keys` a record
+    whose Key is not the query's raises ValueError: the Index named another
+    record than the Data file holds there."""
+    import os
+    from . import record
+    fds, opened = {}, []
+    try:
+        out = []
+        for i, loc in enumerate(located):
+            if loc is None:
+                out.append(None)
+                continue
+            t, off = loc
+            if t not in fds:
+                f = data_files[t]
+                if isinstance(f, int):
+                    fds[t] = f
+                else:
+                    fds[t] = os.open(f, os.O_RDONLY)
+                    opened.append(fds[t])
+            if off < 0:
+                raise ValueError(f"Data offset {off} of table {t} is negative")
+            buf = os.pread(fds[t], read_hint, off)
+            if len(buf) >= record.HEADER_SIZE:
+                _, _, _, _, ks, vs = record._HDR.unpack_from(buf, 0)
+                total = record.HEADER_SIZE + ks + vs
+                if total > len(buf):
+                    buf += os.pread(fds[t], total - len(buf), off + len(buf))
+            if len(buf) < record.HEADER_SIZE:
+                raise EOFError(f"truncated record at offset {off} of table {t}")
+            rec, _ = record.parse(buf, 0)
+            if keys is not None and rec.Key != bytes(keys[i]):
+                raise ValueError(f"the record at offset {off} of table {t} holds another key")
+            out.append(None if rec.IsDeleted() else rec.Value)
+        return out
+    finally:
+        for fd in opened:
+            os.close(fd)
+
+
+def get_many_on_disk(indexed_tables, data_files, keys: Sequence[bytes], resident: Sequence[ResidentTable] = (),
+                     memtable=None):
+    """The engine's get (coreeng.go:79-160, without the LRU step) for a batch
+    of keys over a store whose cold tables keep only their Index and filter on
+    the device: the memtable and the `resident` tables answer first, as
+    get_many has them; the keys they leave ABSENT are searched in
+    `indexed_tables` (sstable.IndexedTable, in search order: every resident
+    table is ahead of every Index-only one) by nkv_locate_dev with overlay; and
+    each LOCATED key costs one pread of its record from data_files[table]
+    (read_located).  Returns per key the Value bytes, or None where no table
+    holds the key or the answer is a tombstone."""
+    if len(data_files) != len(indexed_tables):
+        raise ValueError("get_many_on_disk: one Data file per Index-only table")
+    if not indexed_tables:
+        return get_many(resident, keys, memtable=memtable)
+    if len(keys) == 0:
+        return []
+    return get_many(resident, keys, memtable=memtable, _indexed=list(indexed_tables), _data_files=list(data_files))
 
 
 # ---------------------------------------------------------------------------

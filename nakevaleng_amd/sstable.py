@@ -13,6 +13,9 @@
   make_table_secondaries_from_records   MakeTableSecondaries over a serialized
                              Data table: Index, Summary and Metadata files
                              (and the filter's bits) from one upload
+  open_index / open_index_files   the readers' first half: an Index/Summary pair
+                             parsed and validated on the device (nkv_index_open_dev),
+                             the Index kept resident for lsmtree.locate_many
   open_data_table            the Deserialize loop lsmtree.merge runs over a Data file
                              (lsmtree.go:137-231): the records' sizes from the bytes alone
   table_filename             util/filename.Table             filename.go:58-65, 300-309
@@ -282,3 +285,78 @@ def make_table_secondaries_from_records(path: str, dbname: str, summary_page_siz
     _lib.check(L.nkv_write_file(f_meta.encode(), _lib.p8(img), img.size), f"Serialize({f_meta})")
     root_at = (L.nkv_total_nodes(n) - 1) * 20
     return d_nodes.cpu().numpy()[root_at:root_at + 20].tobytes(), bf
+
+
+# ---------------------------------------------------------------------------
+# Index tables opened on the device (nkv_index_open_dev): the key directory of
+# lsmtree.locate_many / get_many_on_disk
+
+class IndexedTable:
+    """One table whose Index (and, optionally, filter words) stays on a device
+    while its Data file stays on disk: the Index bytes, the n entry offsets
+    nkv_index_open_dev found, and the filter.  The handle keeps the torch
+    tensors alive; drop it to free them."""
+
+    def __init__(self, device: int, index, index_len: int, ent_off, n: int, s: int, bits=None, m: int = 0,
+                 k: int = 0, seed0: int = 0):
+        self.device, self.index, self.index_len, self.ent_off = device, index, int(index_len), ent_off
+        self.n, self.s = int(n), int(s)
+        self.bits, self.m, self.k, self.seed0 = bits, int(m), int(k), int(seed0)
+
+    def as_struct(self):
+        return _lib.NkvIndexTable(self.index.data_ptr(), self.index_len, self.ent_off.data_ptr(), self.n,
+                                  self.bits.data_ptr() if self.bits is not None else None, self.m, self.k,
+                                  self.seed0)
+
+
+def open_index(index_bytes, summary_bytes, filter=None, device: Optional[int] = None) -> IndexedTable:
+    """Upload an Index/Summary pair, parse and validate it on the device
+    (nkv_index_open_dev) and keep the Index with its entry offsets; the Summary
+    is dropped, the search does not need it.  `filter` (a BloomFilter) adds the
+    filter's words.  A pair that is not canonical (include/nkv_merkle.h, "index
+    lookup") raises ValueError naming the verdict bit: the reference's one-key
+    reader remains the way to serve it."""
+    import ctypes
+    import torch
+    from . import lsmtree
+    index_bytes, summary_bytes = bytes(index_bytes), bytes(summary_bytes)
+    if not index_bytes or not summary_bytes:
+        raise ValueError("open_index: an empty Index or Summary holds no chain")
+    dev_index = lsmtree.rank_device(device)
+    ctx = _lib.default_context(dev_index)
+    dev = torch.device("cuda", dev_index)
+
+    def up(a):
+        return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).copy()).to(dev)
+
+    d_index, d_summary = up(np.frombuffer(index_bytes, np.uint8)), up(np.frombuffer(summary_bytes, np.uint8))
+    cap = len(index_bytes) // 16
+    d_ent = torch.empty(8 * max(cap, 1), dtype=torch.uint8, device=dev)
+    n, s, verdict = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint32(0)
+    stream = torch.cuda.current_stream(dev)
+    with ctx.on_stream(stream.cuda_stream):
+        _lib.check(_lib.lib().nkv_index_open_dev(ctx.h, d_index.data_ptr(), len(index_bytes), d_summary.data_ptr(),
+                                                 len(summary_bytes), d_ent.data_ptr(), cap, ctypes.byref(n),
+                                                 ctypes.byref(s), ctypes.byref(verdict)), "index open")
+    if verdict.value:
+        bit = verdict.value & -verdict.value
+        raise ValueError(f"open_index: the pair is not canonical: NKV_INDEX_{_lib.INDEX_VERDICTS[bit]} ({bit})")
+    d_ent = d_ent[:8 * n.value].clone()
+    d_bits, m, k, seed0 = None, 0, 0, 0
+    if filter is not None:
+        m, k, seed0 = filter.M, filter.K, filter._seed0
+        words = np.zeros(((m + 31) // 32) * 4, np.uint8)
+        contents = np.frombuffer(bytes(filter.Contents), np.uint8)
+        words[:contents.size] = contents
+        d_bits = up(words)
+    return IndexedTable(dev_index, d_index, len(index_bytes), d_ent, n.value, s.value, d_bits, m, k, seed0)
+
+
+def open_index_files(path: str, dbname: str, level: int, run: int, filter=None,
+                     device: Optional[int] = None) -> IndexedTable:
+    """open_index over <dbname>-<level>-<run>-index.db and -summary.db."""
+    with open(table_filename(path, dbname, level, run, TYPE_INDEX), "rb") as f:
+        index = f.read()
+    with open(table_filename(path, dbname, level, run, TYPE_SUMMARY), "rb") as f:
+        summary = f.read()
+    return open_index(index, summary, filter, device)
