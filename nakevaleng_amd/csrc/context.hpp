@@ -340,6 +340,15 @@ int download_table(nkv_ctx* c, const void* d_table, uint64_t len, const uint64_t
 // The verdict of a validating kernel: the error word to the host and the
 // stream synchronized; NKV_ERR_INVALID if the word is set.
 int read_verdict(nkv_ctx* c, const unsigned int* d_err);
+// The error word of an entry with a nullable d_err: the caller's, or the first
+// word of d_stats; cleared on the stream.  d_stats is grown to 8 bytes at most
+// and grow() never shrinks or moves a buffer that is large enough, so an entry
+// that keeps more words behind this one sizes d_stats for all of them first
+// and its pointers stay good.
+int verdict_word(nkv_ctx* c, uint32_t* d_err, unsigned int** err);
+// The end of such an entry: d_err given, NKV_OK (the caller reads the word);
+// otherwise read_verdict over the word verdict_word handed out.
+int finish_verdict(nkv_ctx* c, const uint32_t* d_err, const unsigned int* err);
 
 // ---- tree.cpp: leaf planning and the tree entries' shared steps ----
 // Level 0 in the plan NKV_OPT_BUCKET picks (host_len: the lengths on the host, nullable)

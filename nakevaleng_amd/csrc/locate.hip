@@ -38,9 +38,9 @@
 // start search of a chunk looks at no more than kChunk positions.  No
 // workgroup waits on another.
 //
-// Locate: k_locate, one lane per query and the tables in order, as k_lookup
-// (lookup.hip): the filter test, the range test against entries 0 and n - 1, a
-// lower bound over ent_off with every probed key read in place.
+// Locate: k_locate, the search layer's kernel (search_dev.hpp) over the entry
+// format: the key lies behind the two fields, and a found entry answers LOCATED
+// with its stored Offset.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -48,7 +48,7 @@
 
 #include "bytes_dev.hpp"
 #include "context.hpp"
-#include "murmur_dev.hpp"
+#include "search_dev.hpp"
 
 using namespace nkv;
 
@@ -58,18 +58,6 @@ constexpr uint64_t kNone = ~uint64_t(0);
 constexpr uint64_t kEnt = 16;  // KeySize + Offset in front of every entry's key
 // verdict bits raised on the device before the host names the stage
 constexpr uint32_t kFlagLink = 1, kFlagPage = 2;
-
-// The entry at img + o lies inside the image of L bytes: its two fields and its
-// key.  Yields KeySize.  The size is compared against the room behind the
-// fields and o + 16 + KeySize is never formed first, so nothing wraps; nothing
-// outside [img, img + L) is read.
-__device__ __forceinline__ bool entry_in(const uint8_t* __restrict__ img, uint64_t L, uint64_t o, uint64_t* ks) {
-    if (o > L || L - o < kEnt) return false;
-    const uint64_t k = ld_le64(img + o);
-    if (k > L - o - kEnt) return false;
-    *ks = k;
-    return true;
-}
 
 __device__ __forceinline__ bool same_bytes(const uint8_t* __restrict__ a, const uint8_t* __restrict__ b, uint64_t n) {
     for (uint64_t i = 0; i < n; ++i)
@@ -235,139 +223,40 @@ __global__ __launch_bounds__(kBlock) void k_order(const uint8_t* __restrict__ I,
 // ---------------------------------------------------------------------------
 // locate
 
-struct Tables {  // kernel argument: the T tables in search order
-    const uint8_t* index[NKV_LOOKUP_MAX_TABLES];
-    uint64_t len[NKV_LOOKUP_MAX_TABLES];
-    const uint64_t* off[NKV_LOOKUP_MAX_TABLES];
-    const uint32_t* bits[NKV_LOOKUP_MAX_TABLES];  // nullptr: every key passes
-    uint64_t M[NKV_LOOKUP_MAX_TABLES];            // fastmod_magic(m)
-    uint32_t n[NKV_LOOKUP_MAX_TABLES], m[NKV_LOOKUP_MAX_TABLES], k[NKV_LOOKUP_MAX_TABLES],
-        seed[NKV_LOOKUP_MAX_TABLES];
-    int T;
-    uint32_t base;
+// The entry format of an Index table: KeySize | Offset | Key; a found entry
+// answers LOCATED and its stored Offset.  An entry whose file says -1 reads as a
+// miss (coreeng.go:138 tests the stored field).
+struct IndexFormat {
+    static constexpr uint64_t kKeyAt = kEntryHdr;
+    static constexpr bool kOverlay = true;
+    NKV_HD static bool key_in(const uint8_t* img, uint64_t L, uint64_t o, uint64_t* ks) {
+        return entry_in(img, L, o, ks);
+    }
+    int overlay;        // the call's: answered queries are left as they are
+    int64_t* data_off;  // the call's output
+    int64_t d = -1;     // this query's
+    __device__ bool answer(const uint8_t* ent, uint8_t* st) {
+        const int64_t stored = int64_t(ld_le64(ent + 8));
+        if (stored == -1) return false;
+        d = stored;
+        *st = NKV_GET_LOCATED;
+        return true;
+    }
+    __device__ void store(uint64_t i) const { data_off[i] = d; }
 };
 
-struct Query {
-    const uint8_t* key;
-    uint64_t len;
-    uint64_t pfx;  // first 8 key bytes, big-endian, zero-padded
-};
-
-constexpr int kBad = 2;  // probe: the entry reaches outside the image
-
-// bytes.Compare(query, key of entry j): -1, 0, 1, or kBad.
-__device__ __forceinline__ int probe(const Query& Q, const uint8_t* __restrict__ I, uint64_t L,
-                                     const uint64_t* __restrict__ off, uint64_t j, uint64_t* at) {
-    const uint64_t o = off[j];
-    uint64_t ks;
-    if (!entry_in(I, L, o, &ks)) return kBad;
-    *at = o;
-    const uint8_t* ek = I + o + kEnt;
-    return cmp_prefixed(Q.pfx, Q.len, Q.key + 8, key_prefix(ek, ks), ks, ek + 8);
-}
-
-// One table's search: the stage it ends at and, when FOUND, the entry's index
-// and stored Offset.  An entry whose file says -1 reads as a miss (coreeng.go:138
-// tests the stored field).  A bad probe ends the search at INDEX and raises *bad.
-__device__ __forceinline__ uint32_t search(const Tables& R, int t, const Query& Q, uint64_t* found, int64_t* data_off,
-                                           bool* bad) {
-    const uint32_t* bits = R.bits[t];
-    if (bits && !filter_query(Q.key, Q.len, bits, R.m[t], R.M[t], R.k[t], R.seed[t])) return NKV_STAGE_FILTER;
-    const uint8_t* I = R.index[t];
-    const uint64_t L = R.len[t];
-    const uint64_t* off = R.off[t];
-    const uint64_t n = R.n[t];
-    uint64_t at = 0;
-    int c = probe(Q, I, L, off, 0, &at);
-    uint64_t j = 0;
-    if (c < 0) return NKV_STAGE_SUMMARY;  // key < MinKey
-    if (c == 1 && n > 1) {
-        j = n - 1;
-        c = probe(Q, I, L, off, j, &at);
-    }
-    if (c == 1) return NKV_STAGE_SUMMARY;  // key > MaxKey
-    if (c < 0) {  // K_0 < key < K_(n-1): the first entry in (0, n - 1) whose key is not below the query's
-        uint64_t lo = 1, hi = n - 1;
-        while (lo < hi) {
-            j = lo + (hi - lo) / 2;
-            c = probe(Q, I, L, off, j, &at);
-            if (c == 1) lo = j + 1;
-            else if (c < 0) hi = j;
-            else break;  // equal, or a bad entry
-        }
-    }
-    if (c == kBad) *bad = true;
-    if (c != 0) return NKV_STAGE_INDEX;
-    const int64_t stored = int64_t(ld_le64(I + at + 8));
-    if (stored == -1) return NKV_STAGE_INDEX;
-    *found = j;
-    *data_off = stored;
-    return NKV_STAGE_FOUND;
-}
-
-// Every wave with a query keeps its 64 lanes busy: lanes past q redo the last
-// query and store nothing.
 __global__ __launch_bounds__(kBlock) void k_locate(Tables R, const uint8_t* __restrict__ keys,
                                                    const uint64_t* __restrict__ koff,
                                                    const uint64_t* __restrict__ klen, uint64_t q, int overlay,
                                                    uint64_t* __restrict__ hit, int64_t* __restrict__ data_off,
                                                    uint8_t* __restrict__ status, uint8_t* __restrict__ stage,
                                                    unsigned int* __restrict__ err) {
-    const uint64_t gi = uint64_t(blockIdx.x) * kBlock + threadIdx.x;
-    if ((gi & ~uint64_t(63)) >= q) return;
-    const bool live = gi < q;
-    const uint64_t i = live ? gi : q - 1;
-    const bool answered = overlay && status[i] != NKV_GET_ABSENT;  // left exactly as it was
-    Query Q;
-    Q.key = keys + koff[i];
-    Q.len = klen[i];
-    Q.pfx = key_prefix(Q.key, Q.len);
-    uint64_t h = kNone;
-    int64_t d = -1;
-    uint8_t st = NKV_GET_ABSENT;
-    bool bad = false;
-    for (int t = 0; t < R.T; ++t) {
-        uint32_t sg = NKV_STAGE_NOT_SEARCHED;
-        if (h == kNone && !answered) {
-            uint64_t j = 0;
-            sg = search(R, t, Q, &j, &d, &bad);
-            if (sg == NKV_STAGE_FOUND) {
-                h = (uint64_t(R.base + uint32_t(t)) << 32) | j;
-                st = NKV_GET_LOCATED;
-            }
-        }
-        if (stage && live) stage[i * uint64_t(R.T) + t] = uint8_t(sg);
-    }
-    if (live && !answered) {
-        hit[i] = h;
-        data_off[i] = d;
-        status[i] = st;
-        if (bad) atomicOr(err, 1u);
-    }
+    search_tables(R, IndexFormat{overlay, data_off}, keys, koff, klen, q, hit, status, stage, err);
 }
 
-int pack_tables(const nkv_index_table* tables, int T, uint32_t table_base, Tables* R) {
-    if (!tables || T < 1 || T > NKV_LOOKUP_MAX_TABLES) return NKV_ERR_INVALID;
-    if (uint64_t(table_base) + uint64_t(T) > 65536) return NKV_ERR_INVALID;
-    *R = Tables{};
-    R->T = T;
-    R->base = table_base;
-    for (int t = 0; t < T; ++t) {
-        const nkv_index_table& u = tables[t];
-        if (u.n < 1 || u.n > kMaxN || !u.index || !u.ent_off) return NKV_ERR_INVALID;
-        if (u.bits && u.k && u.m == 0) return NKV_ERR_INVALID;
-        R->index[t] = static_cast<const uint8_t*>(u.index);
-        R->len[t] = u.index_len;
-        R->off[t] = u.ent_off;
-        R->n[t] = uint32_t(u.n);
-        const bool filtered = u.bits && u.k;  // k = 0: Query's loop has no bit to miss
-        R->bits[t] = filtered ? static_cast<const uint32_t*>(u.bits) : nullptr;
-        R->m[t] = filtered ? u.m : 1;
-        R->M[t] = fastmod_magic(R->m[t]);
-        R->k[t] = filtered ? u.k : 0;
-        R->seed[t] = u.seed0;
-    }
-    return NKV_OK;
+// nkv_index_table as the search layer reads it
+TableView view_of(const nkv_index_table& u) {
+    return {u.index, u.index_len, u.ent_off, u.n, u.bits, u.m, u.k, u.seed0};
 }
 
 // ---------------------------------------------------------------------------
@@ -553,21 +442,17 @@ int nkv_locate_dev(nkv_ctx* c, const nkv_index_table* tables, int T, uint32_t ta
                    int64_t* d_data_off, uint8_t* d_status, uint8_t* d_stage, uint32_t* d_err) try {
     TRY(bind(c));
     Tables R;
-    TRY(pack_tables(tables, T, table_base, &R));
+    TRY(pack_tables(tables, T, table_base, view_of, &R));
     if (q > kMaxN) return NKV_ERR_INVALID;
     if (q == 0) return NKV_OK;
     if (!d_keys || !d_koff || !d_klen || !d_hit || !d_data_off || !d_status) return NKV_ERR_INVALID;
-    unsigned int* err = d_err;
-    if (!err) {
-        TRY(grow(c->d_stats, 8));
-        err = static_cast<unsigned int*>(c->d_stats.p);
-    }
-    HIPTRY(hipMemsetAsync(err, 0, 4, c->stream));
+    unsigned int* err;
+    TRY(verdict_word(c, d_err, &err));
     hipLaunchKernelGGL(k_locate, dim3(blocks_for(q)), dim3(kBlock), 0, c->stream, R,
                        static_cast<const uint8_t*>(d_keys), d_koff, d_klen, q, overlay ? 1 : 0, d_hit, d_data_off,
                        d_status, d_stage, err);
     HIPTRY(hipGetLastError());
-    return d_err ? NKV_OK : read_verdict(c, err);
+    return finish_verdict(c, d_err, err);
 } NKV_CATCH
 
 }  // extern "C"

@@ -8,13 +8,9 @@
 // Data table the Summary and Index steps have a closed form: the Summary
 // refuses a key outside [K_0, K_(n-1)], the Index a key that no record holds.
 //
-//   k_lookup        one lane per query, the tables in order: the filter test is
-//                   mm_states (murmur_dev.hpp) over the query key, the range
-//                   test reads the keys of records 0 and n - 1, and a lower
-//                   bound over rec_off reads every probed key in place.  Keys
-//                   are compared by an 8-byte big-endian prefix first and byte
-//                   by byte only where the prefixes are equal (record_dev.hpp
-//                   cmp_prefixed).
+//   k_lookup        the search layer's kernel (search_dev.hpp) over the record
+//                   format: the key lies behind the 30-byte header, and a found
+//                   record answers LIVE or TOMBSTONE.
 //   k_value_measure one lane per query: the found record's Value span, checked
 //                   against its stream.
 //   scan            exclusive sums of the lengths = the packed offsets
@@ -32,115 +28,37 @@
 
 #include "bytes_dev.hpp"
 #include "context.hpp"
-#include "murmur_dev.hpp"
+#include "search_dev.hpp"
 
 using namespace nkv;
 
 namespace {
 
-constexpr uint64_t kNone = ~uint64_t(0);
 constexpr uint32_t kCopyTile = 16384;  // output bytes per workgroup
 constexpr uint32_t kCopyChunk = 16;    // output bytes per lane and step
 constexpr uint32_t kCopyList = 1024;   // queries of a tile kept in LDS
 
-struct Tables {  // kernel argument: the T tables in search order
-    const uint8_t* stream[NKV_LOOKUP_MAX_TABLES];
-    uint64_t len[NKV_LOOKUP_MAX_TABLES];
-    const uint64_t* off[NKV_LOOKUP_MAX_TABLES];
-    const uint32_t* bits[NKV_LOOKUP_MAX_TABLES];  // nullptr: every key passes
-    uint64_t M[NKV_LOOKUP_MAX_TABLES];            // fastmod_magic(m)
-    uint32_t n[NKV_LOOKUP_MAX_TABLES], m[NKV_LOOKUP_MAX_TABLES], k[NKV_LOOKUP_MAX_TABLES],
-        seed[NKV_LOOKUP_MAX_TABLES];
-    int T;
+// The entry format of a Data table: a record, its key behind the 30-byte
+// header; a found record answers LIVE or TOMBSTONE from its Status byte.
+struct RecordFormat {
+    static constexpr uint64_t kKeyAt = kHdr;
+    static constexpr bool kOverlay = false;
+    NKV_HD static bool key_in(const uint8_t* s, uint64_t L, uint64_t o, uint64_t* ks) {
+        return key_span_in(s, L, o, ks);
+    }
+    __device__ bool answer(const uint8_t* rec, uint8_t* st) const {
+        *st = status_answer(rec[kAtStatus]);
+        return true;
+    }
+    __device__ void store(uint64_t) const {}
 };
 
-struct Query {
-    const uint8_t* key;
-    uint64_t len;
-    uint64_t pfx;  // first 8 key bytes, big-endian, zero-padded
-};
-
-constexpr int kBad = 2;  // probe: the record's header or key span leaves the stream
-
-// bytes.Compare(query, key of record j): -1, 0, 1, or kBad.  Nothing outside
-// [s, s + L) is read.
-__device__ __forceinline__ int probe(const Query& Q, const uint8_t* __restrict__ s, uint64_t L,
-                                     const uint64_t* __restrict__ off, uint64_t j) {
-    const uint64_t o = off[j];
-    uint64_t ks;
-    if (!key_span_in(s, L, o, &ks)) return kBad;
-    const uint8_t* rk = s + o + kHdr;
-    return cmp_prefixed(Q.pfx, Q.len, Q.key + 8, key_prefix(rk, ks), ks, rk + 8);
-}
-
-// One table's search: the stage it ends at and, when FOUND, the record index.
-// A bad probe ends the search at INDEX (no equal key) and raises *bad.
-__device__ __forceinline__ uint32_t search(const Tables& R, int t, const Query& Q, uint64_t* found, bool* bad) {
-    const uint32_t* bits = R.bits[t];
-    if (bits && !filter_query(Q.key, Q.len, bits, R.m[t], R.M[t], R.k[t], R.seed[t])) return NKV_STAGE_FILTER;
-    const uint8_t* s = R.stream[t];
-    const uint64_t L = R.len[t];
-    const uint64_t* off = R.off[t];
-    const uint64_t n = R.n[t];
-    int c = probe(Q, s, L, off, 0);
-    uint64_t j = 0;
-    if (c < 0) return NKV_STAGE_SUMMARY;  // key < MinKey
-    if (c == 1 && n > 1) {
-        j = n - 1;
-        c = probe(Q, s, L, off, j);
-    }
-    if (c == 1) return NKV_STAGE_SUMMARY;  // key > MaxKey
-    if (c < 0) {  // K_0 < key < K_(n-1): the first record in (0, n - 1) whose key is not below the query's
-        uint64_t lo = 1, hi = n - 1;
-        while (lo < hi) {
-            j = lo + (hi - lo) / 2;
-            c = probe(Q, s, L, off, j);
-            if (c == 1) lo = j + 1;
-            else if (c < 0) hi = j;
-            else break;  // equal, or a bad record
-        }
-    }
-    if (c == kBad) *bad = true;
-    if (c != 0) return NKV_STAGE_INDEX;
-    *found = j;
-    return NKV_STAGE_FOUND;
-}
-
-// Every wave with a query keeps its 64 lanes busy: lanes past q redo the last
-// query and store nothing.
 __global__ __launch_bounds__(kBlock) void k_lookup(Tables R, const uint8_t* __restrict__ keys,
                                                    const uint64_t* __restrict__ koff,
                                                    const uint64_t* __restrict__ klen, uint64_t q,
                                                    uint64_t* __restrict__ hit, uint8_t* __restrict__ status,
                                                    uint8_t* __restrict__ stage, unsigned int* __restrict__ err) {
-    const uint64_t gi = uint64_t(blockIdx.x) * kBlock + threadIdx.x;
-    if ((gi & ~uint64_t(63)) >= q) return;
-    const bool live = gi < q;
-    const uint64_t i = live ? gi : q - 1;
-    Query Q;
-    Q.key = keys + koff[i];
-    Q.len = klen[i];
-    Q.pfx = key_prefix(Q.key, Q.len);
-    uint64_t h = kNone;
-    uint8_t st = NKV_GET_ABSENT;
-    bool bad = false;
-    for (int t = 0; t < R.T; ++t) {
-        uint32_t sg = NKV_STAGE_NOT_SEARCHED;
-        if (h == kNone) {
-            uint64_t j = 0;
-            sg = search(R, t, Q, &j, &bad);
-            if (sg == NKV_STAGE_FOUND) {
-                h = (uint64_t(t) << 32) | j;
-                st = (R.stream[t][R.off[t][j] + kAtStatus] & 1) ? NKV_GET_TOMBSTONE : NKV_GET_LIVE;
-            }
-        }
-        if (stage && live) stage[i * uint64_t(R.T) + t] = uint8_t(sg);
-    }
-    if (live) {
-        hit[i] = h;
-        status[i] = st;
-        if (bad) atomicOr(err, 1u);
-    }
+    search_tables(R, RecordFormat{}, keys, koff, klen, q, hit, status, stage, err);
 }
 
 // len[i] / src[i]: the Value of LIVE hit i (0 bytes for every other query)
@@ -155,7 +73,7 @@ __global__ __launch_bounds__(kBlock) void k_value_measure(Tables R, const uint64
         const uint64_t h = hit[i], t = h >> 32, j = h & 0xFFFFFFFFull;
         bool bad = t >= uint64_t(R.T) || j >= R.n[t < uint64_t(R.T) ? t : 0];
         if (!bad) {
-            const uint8_t* s = R.stream[t];
+            const uint8_t* s = R.img[t];
             const uint64_t o = R.off[t][j];
             uint64_t ks, v;
             bad = !record_span_in(s, R.len[t], o, &ks, &v);
@@ -250,27 +168,9 @@ __global__ __launch_bounds__(kBlock) void k_value_copy(uint8_t* __restrict__ out
     }
 }
 
-// The tables as the kernels take them; NKV_ERR_INVALID for what the header refuses.
-int pack_tables(const nkv_lookup_table* tables, int T, Tables* R) {
-    if (!tables || T < 1 || T > NKV_LOOKUP_MAX_TABLES) return NKV_ERR_INVALID;
-    *R = Tables{};
-    R->T = T;
-    for (int t = 0; t < T; ++t) {
-        const nkv_lookup_table& u = tables[t];
-        if (u.n < 1 || u.n > kMaxN || !u.stream || !u.rec_off) return NKV_ERR_INVALID;
-        if (u.bits && u.k && u.m == 0) return NKV_ERR_INVALID;
-        R->stream[t] = static_cast<const uint8_t*>(u.stream);
-        R->len[t] = u.stream_len;
-        R->off[t] = u.rec_off;
-        R->n[t] = uint32_t(u.n);
-        const bool filtered = u.bits && u.k;  // k = 0: Query's loop has no bit to miss
-        R->bits[t] = filtered ? static_cast<const uint32_t*>(u.bits) : nullptr;
-        R->m[t] = filtered ? u.m : 1;
-        R->M[t] = fastmod_magic(R->m[t]);
-        R->k[t] = filtered ? u.k : 0;
-        R->seed[t] = u.seed0;
-    }
-    return NKV_OK;
+// nkv_lookup_table as the search layer reads it
+TableView view_of(const nkv_lookup_table& u) {
+    return {u.stream, u.stream_len, u.rec_off, u.n, u.bits, u.m, u.k, u.seed0};
 }
 
 }  // namespace
@@ -282,20 +182,16 @@ int nkv_lookup_dev(nkv_ctx* c, const nkv_lookup_table* tables, int T, const void
                    uint32_t* d_err) try {
     TRY(bind(c));
     Tables R;
-    TRY(pack_tables(tables, T, &R));
+    TRY(pack_tables(tables, T, 0, view_of, &R));
     if (q > kMaxN) return NKV_ERR_INVALID;
     if (q == 0) return NKV_OK;
     if (!d_keys || !d_koff || !d_klen || !d_hit || !d_status) return NKV_ERR_INVALID;
-    unsigned int* err = d_err;
-    if (!err) {
-        TRY(grow(c->d_stats, 8));
-        err = static_cast<unsigned int*>(c->d_stats.p);
-    }
-    HIPTRY(hipMemsetAsync(err, 0, 4, c->stream));
+    unsigned int* err;
+    TRY(verdict_word(c, d_err, &err));
     hipLaunchKernelGGL(k_lookup, dim3(blocks_for(q)), dim3(kBlock), 0, c->stream, R,
                        static_cast<const uint8_t*>(d_keys), d_koff, d_klen, q, d_hit, d_status, d_stage, err);
     HIPTRY(hipGetLastError());
-    return d_err ? NKV_OK : read_verdict(c, err);
+    return finish_verdict(c, d_err, err);
 } NKV_CATCH
 
 int nkv_lookup_values_dev(nkv_ctx* c, const nkv_lookup_table* tables, int T, const uint64_t* d_hit,
@@ -305,7 +201,7 @@ int nkv_lookup_values_dev(nkv_ctx* c, const nkv_lookup_table* tables, int T, con
     if (!out_len) return NKV_ERR_INVALID;
     *out_len = 0;
     Tables R;
-    TRY(pack_tables(tables, T, &R));
+    TRY(pack_tables(tables, T, 0, view_of, &R));
     if (q > kMaxN) return NKV_ERR_INVALID;
     const bool query = !d_out;
     if (q == 0) {  // no Value: the one offset entry is 0

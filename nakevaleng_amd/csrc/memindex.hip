@@ -38,20 +38,20 @@
 //                   which ShouldFlush holds (only a write where it starts to
 //                   hold, or the batch's first, takes the atomicMin).
 //   k_mem_state     one lane: Count, memusage, the indexed count, flush_at.
-// Find: one lane per query probes and compares with the record at the slot's
-// latest word, then reads that record's Status.
+// Find: one lane per query (search_dev.hpp's Query) probes and compares with
+// the record at the slot's latest word; that record's Status and the hit word
+// are the search layer's answers.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "context.hpp"
-#include "murmur_dev.hpp"
+#include "search_dev.hpp"
 
 using namespace nkv;
 
 namespace {
 
 constexpr uint64_t kEmpty = ~uint64_t(0);
-constexpr uint64_t kNone = ~uint64_t(0);
 constexpr uint32_t kSeed = 0x6d656d74u;  // the index's murmur3 seed
 constexpr unsigned kErrRecord = 1;  // a record's span, or where it ends
 constexpr unsigned kErrCount = 2;   // the indexed count is not n_done
@@ -204,11 +204,9 @@ __global__ __launch_bounds__(kBlock) void k_mem_find(Log G, uint32_t n, const ui
                                                      uint8_t* __restrict__ status, unsigned int* err) {
     const uint64_t i = uint64_t(blockIdx.x) * kBlock + threadIdx.x;
     if (i >= q) return;
-    const uint8_t* key = keys + koff[i];
-    const uint64_t kl = klen[i];
-    const uint64_t pfx = key_prefix(key, kl);
-    uint32_t s = hash_key(key, kl) & mask;
-    uint64_t found = kNone;
+    const Query Q = query_of(keys, koff, klen, i);
+    uint32_t s = hash_key(Q.key, Q.len) & mask;
+    uint64_t found = kNoHit;
     uint8_t st = NKV_GET_ABSENT;
     bool bad = false, ended = false;
     for (uint64_t step = 0; step <= mask; ++step, s = (s + 1) & mask) {
@@ -223,19 +221,19 @@ __global__ __launch_bounds__(kBlock) void k_mem_find(Log G, uint32_t n, const ui
             bad = true;  // no match; nothing outside the log is read
             continue;
         }
-        if (same_key(pfx, kl, key, G.s + o + kHdr, ks)) {
+        if (same_key(Q.pfx, Q.len, Q.key, G.s + o + kHdr, ks)) {
             found = latest;
-            st = (G.s[o + kAtStatus] & 1) ? NKV_GET_TOMBSTONE : NKV_GET_LIVE;
+            st = status_answer(G.s[o + kAtStatus]);
             ended = true;
             break;
         }
     }
     if (bad || !ended) atomicOr(err, 1u);
-    if (found != kNone) {
-        hit[i] = (uint64_t(table_id) << 32) | found;
+    if (found != kNoHit) {
+        hit[i] = hit_word(table_id, found);
         status[i] = st;
     } else if (!overlay) {
-        hit[i] = kNone;
+        hit[i] = kNoHit;
         status[i] = NKV_GET_ABSENT;
     }
 }
@@ -287,15 +285,15 @@ int nkv_memtable_add_dev(nkv_ctx* c, const void* d_log, uint64_t log_len, const 
     size_t tb = 0;
     HIPTRY(scan_exclusive_u64(flag, xflag, m, nullptr, &tb, c->stream));
     TRY(grow(c->d_tmp, tb));
-    TRY(grow(c->d_stats, 16));  // [err | pad | flush_at]
-    unsigned int* err = d_err ? d_err : static_cast<unsigned int*>(c->d_stats.p);
+    TRY(grow(c->d_stats, 16));  // [err | pad | flush_at]: sized here, before verdict_word takes its word
     unsigned long long* flush_at = static_cast<unsigned long long*>(c->d_stats.p) + 1;
     const uint32_t n0 = uint32_t(n_done), n1 = uint32_t(n), mask = uint32_t(slots - 1);
     const dim3 grid(blocks_for(m)), block(kBlock);
 
     // with NKV_TIMING_EVENTS: "leaf" = validate + insert + flags, "reduce" = scans + flush point + state
     TRY(mark(c, 0));
-    HIPTRY(hipMemsetAsync(err, 0, 4, c->stream));
+    unsigned int* err;
+    TRY(verdict_word(c, d_err, &err));
     HIPTRY(hipMemsetAsync(flush_at, 0xFF, 8, c->stream));
     hipLaunchKernelGGL(k_mem_validate, grid, block, 0, c->stream, G, n0, n1, d_state, size, err);
     HIPTRY(hipGetLastError());
@@ -315,7 +313,7 @@ int nkv_memtable_add_dev(nkv_ctx* c, const void* d_log, uint64_t log_len, const 
                        flush_at, err);
     HIPTRY(hipGetLastError());
     TRY(mark(c, 2));
-    return d_err ? NKV_OK : read_verdict(c, err);
+    return finish_verdict(c, d_err, err);
 } NKV_CATCH
 
 int nkv_memtable_find_dev(nkv_ctx* c, const void* d_log, uint64_t log_len, const uint64_t* d_rec_off, uint64_t n,
@@ -328,18 +326,14 @@ int nkv_memtable_find_dev(nkv_ctx* c, const void* d_log, uint64_t log_len, const
     if (n && (!d_log || !d_rec_off)) return NKV_ERR_INVALID;
     if (q == 0) return NKV_OK;
     if (!d_keys || !d_koff || !d_klen || !d_hit || !d_status) return NKV_ERR_INVALID;
-    unsigned int* err = d_err;
-    if (!err) {
-        TRY(grow(c->d_stats, 8));
-        err = static_cast<unsigned int*>(c->d_stats.p);
-    }
     const Log G{static_cast<const uint8_t*>(d_log), log_len, d_rec_off};
-    HIPTRY(hipMemsetAsync(err, 0, 4, c->stream));
+    unsigned int* err;
+    TRY(verdict_word(c, d_err, &err));
     hipLaunchKernelGGL(k_mem_find, dim3(blocks_for(q)), dim3(kBlock), 0, c->stream, G, uint32_t(n),
                        static_cast<const uint64_t*>(d_index), uint32_t(slots - 1), static_cast<const uint8_t*>(d_keys),
                        d_koff, d_klen, q, table_id, overlay, d_hit, d_status, err);
     HIPTRY(hipGetLastError());
-    return d_err ? NKV_OK : read_verdict(c, err);
+    return finish_verdict(c, d_err, err);
 } NKV_CATCH
 
 }  // extern "C"

@@ -1,6 +1,6 @@
 // murmur_dev.hpp -- MurmurHash3_x86_32 (spaolacci/murmur3 v1.1.0 Sum32) on the
 // device, several seeds at once, shared by the filter build (bloom.hip) and the
-// filter test of the point lookups (lookup.hip, locate.hip).
+// filter test of the point lookups (search_dev.hpp) and the memtable's hash.
 //
 // The key's 4-byte little-endian blocks come from aligned dword loads funnelled
 // by the key's byte offset (v_alignbyte), so any alignment works and no load

@@ -1,8 +1,8 @@
 // record_dev.hpp -- the record format and the key order, once, for every
-// kernel and host function that reads records: the header's layout, the two
-// bounds checks that keep a wild offset or size from reaching a load, the
-// dense entry the merge and the flush validate, and bytes.Compare by an
-// 8-byte prefix.  The functions are pure and compile as plain host C++ too
+// kernel and host function that reads records: the header's layout, the
+// bounds checks that keep a wild offset or size from reaching a load (a
+// record's, and an Index entry's beside them), the dense entry the merge and
+// the flush validate, and bytes.Compare by an 8-byte prefix.  The functions are pure and compile as plain host C++ too
 // (tests/cpp/test_record_layer.cpp).
 #pragma once
 #include <stdint.h>
@@ -55,6 +55,18 @@ NKV_HD inline bool key_span_in(const uint8_t* s, uint64_t L, uint64_t o, uint64_
     if (!header_in(o, L)) return false;
     const uint64_t k = ld_le64(s + o + kAtKeySize);
     if (k > L - o - kHdr) return false;
+    *ks = k;
+    return true;
+}
+
+// The same check for an Index or Summary entry, KeySize u64 | Offset i64 | Key:
+// the entry at img + o lies inside the image of L bytes, its two fields and
+// its key.  Yields KeySize.
+constexpr uint64_t kEntryHdr = 16;  // KeySize + Offset in front of every entry's key
+NKV_HD inline bool entry_in(const uint8_t* img, uint64_t L, uint64_t o, uint64_t* ks) {
+    if (o > L || L - o < kEntryHdr) return false;
+    const uint64_t k = ld_le64(img + o);
+    if (k > L - o - kEntryHdr) return false;
     *ks = k;
     return true;
 }

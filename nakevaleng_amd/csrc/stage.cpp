@@ -36,6 +36,20 @@ int read_verdict(nkv_ctx* c, const unsigned int* d_err) {
     return h ? NKV_ERR_INVALID : NKV_OK;
 }
 
+int verdict_word(nkv_ctx* c, uint32_t* d_err, unsigned int** err) {
+    *err = d_err;
+    if (!d_err) {
+        TRY(grow(c->d_stats, 8));
+        *err = static_cast<unsigned int*>(c->d_stats.p);
+    }
+    HIPTRY(hipMemsetAsync(*err, 0, 4, c->stream));
+    return NKV_OK;
+}
+
+int finish_verdict(nkv_ctx* c, const uint32_t* d_err, const unsigned int* err) {
+    return d_err ? NKV_OK : read_verdict(c, err);
+}
+
 // Plain copies from the caller's (pageable) memory, not the pipelined Stager:
 // the route of nkv_sort_records, nkv_merge_records and
 // nkv_index_summary_from_records.  Moving them onto the Stager (stage_records)

@@ -41,6 +41,8 @@ from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
+from ._dev import pack_keys, u8, up, up_opt
+
 Table = Tuple[bytes, np.ndarray]  # (Data-table stream, RecSize per record)
 
 
@@ -205,12 +207,6 @@ def compact(tables: Sequence[Table], device=None, seed: Optional[int] = None,
     L = _lib.lib()
     dev = torch.device("cuda", dev_index)
 
-    def up(a):
-        return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).copy()).to(dev)
-
-    def u8(nbytes):
-        return torch.zeros(max(int(nbytes), 16), dtype=torch.uint8, device=dev)
-
     stream = torch.cuda.current_stream(dev)
     with ctx.on_stream(stream.cuda_stream):
         runs = (_lib.NkvRun * k)()
@@ -222,31 +218,43 @@ def compact(tables: Sequence[Table], device=None, seed: Optional[int] = None,
             if n == 0:
                 runs[r] = _lib.NkvRun(None, nbytes, None, 0)
                 continue
-            d_data = up(np.frombuffer(bytes(data), np.uint8))
-            d_size, d_off = up(sizes), u8(8 * n)
-            _lib.check(L.nkv_record_offsets_dev(ctx.h, d_size.data_ptr(), n, d_off.data_ptr()))
-            d_nodes, d_crc, d_stats = u8(L.nkv_total_nodes(n) * 20), u8(4 * n), u8(24)
-            _lib.check(L.nkv_tree_verify_records_dev(ctx.h, d_data.data_ptr(), nbytes, d_off.data_ptr(), n,
-                                                     d_nodes.data_ptr(), d_crc.data_ptr(), d_stats.data_ptr()),
-                       "compaction read")
-            bad, first, hdr = d_stats.cpu().numpy().view(np.uint64).tolist()
-            if hdr:
-                raise _lib.NkvError(_lib.NKV_ERR_INVALID, f"compaction read of run {r}")
-            if bad:
-                got = int(d_crc.cpu().numpy().view(np.uint32)[first])
-                stored = int(np.frombuffer(bytes(data), "<u4", 1, int(sizes[:first].sum()))[0])
-                raise ValueError(f"Bad Record checksum (got {got}, expected {stored})")
+            d_data, d_off = _checked_upload(ctx, dev, data, sizes, "compaction read", r)
             runs[r] = _lib.NkvRun(d_data.data_ptr(), nbytes, d_off.data_ptr(), n)
             keep += [d_data, d_off]
             total += nbytes
             n_all += n
-        d_out, d_out_off, d_out_src = u8(total), u8(8 * n_all), u8(8 * n_all)
+        d_out, d_out_off, d_out_src = u8(dev, total), u8(dev, 8 * n_all), u8(dev, 8 * n_all)
         n_out, out_len = ctypes.c_uint64(0), ctypes.c_uint64(0)
         _lib.check(L.nkv_merge_records_dev(ctx.h, runs, k, d_out.data_ptr(), total, d_out_off.data_ptr(),
                                            d_out_src.data_ptr(), ctypes.byref(n_out), ctypes.byref(out_len)),
                    "compaction merge")
         return _table_secondaries(ctx, dev_index, stream, d_out, d_out_off, d_out_src, n_out.value, out_len.value,
                                   "compaction", seed, false_positive_rate, summary_page_size, resident)
+
+
+def _checked_upload(ctx, dev, data, sizes, label, run=None):
+    """The read in front of compact's merge and flush_log's sort, on the
+    context's stream: one run's bytes and RecSize array to the device, its
+    record offsets (nkv_record_offsets_dev) and every record's Crc checked
+    (nkv_tree_verify_records_dev).  `label` (and `run`, for compact) name the
+    step in the error text.  Returns (stream tensor, offsets tensor)."""
+    from . import _lib
+    L = _lib.lib()
+    n, nbytes = int(sizes.size), len(data)
+    d_data = up(dev, np.frombuffer(bytes(data), np.uint8))
+    d_size, d_off = up(dev, sizes), u8(dev, 8 * n)
+    _lib.check(L.nkv_record_offsets_dev(ctx.h, d_size.data_ptr(), n, d_off.data_ptr()))
+    d_nodes, d_crc, d_stats = u8(dev, L.nkv_total_nodes(n) * 20), u8(dev, 4 * n), u8(dev, 24)
+    _lib.check(L.nkv_tree_verify_records_dev(ctx.h, d_data.data_ptr(), nbytes, d_off.data_ptr(), n,
+                                             d_nodes.data_ptr(), d_crc.data_ptr(), d_stats.data_ptr()), label)
+    bad, first, hdr = d_stats.cpu().numpy().view(np.uint64).tolist()
+    if hdr:
+        raise _lib.NkvError(_lib.NKV_ERR_INVALID, label if run is None else f"{label} of run {run}")
+    if bad:
+        got = int(d_crc.cpu().numpy().view(np.uint32)[first])
+        stored = int(np.frombuffer(bytes(data), "<u4", 1, int(sizes[:first].sum()))[0])
+        raise ValueError(f"Bad Record checksum (got {got}, expected {stored})")
+    return d_data, d_off
 
 
 def _table_secondaries(ctx, dev_index, stream, d_out, d_out_off, d_out_src, n, nbytes, what, seed,
@@ -263,20 +271,17 @@ def _table_secondaries(ctx, dev_index, stream, d_out, d_out_off, d_out_src, n, n
     L = _lib.lib()
     dev = torch.device("cuda", dev_index)
 
-    def u8(nbytes):
-        return torch.zeros(max(int(nbytes), 16), dtype=torch.uint8, device=dev)
-
     if n == 0:
         raise MerkleTreeError("cannot build Merkle Tree from 0 nodes")
-    d_nodes, d_img = u8(L.nkv_total_nodes(n) * 20), u8(L.nkv_bfs_size(n))
-    d_err = u8(4)
+    d_nodes, d_img = u8(dev, L.nkv_total_nodes(n) * 20), u8(dev, L.nkv_bfs_size(n))
+    d_err = u8(dev, 4)
     _lib.check(L.nkv_tree_from_records_dev(ctx.h, d_out.data_ptr(), nbytes, d_out_off.data_ptr(), n,
                                            d_nodes.data_ptr(), d_err.data_ptr()), f"{what} Merkle step")
     _lib.check(L.nkv_bfs_image_dev(ctx.h, d_nodes.data_ptr(), n, d_img.data_ptr()), "Serialize image")
     bf = d_bits = None
     if seed is not None:
         bf = bloomfilter.New(n, false_positive_rate, seed=seed, ctx=ctx)
-        d_bits = u8(((bf.M + 31) // 32) * 4)
+        d_bits = u8(dev, ((bf.M + 31) // 32) * 4)
         _lib.check(L.nkv_bloom_insert_records_dev(ctx.h, d_out.data_ptr(), nbytes, d_out_off.data_ptr(), n,
                                                   bf.M, bf.K, bf.HashSeeds[0] if bf.K else 0,
                                                   d_bits.data_ptr()), f"{what} filter")
@@ -362,31 +367,10 @@ def flush_log(log: Table, device=None, seed: Optional[int] = None, false_positiv
         raise MerkleTreeError("cannot build Merkle Tree from 0 nodes")
     dev_index = rank_device(device)
     ctx = _lib.default_context(dev_index)
-    L = _lib.lib()
     dev = torch.device("cuda", dev_index)
-
-    def up(a):
-        return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).copy()).to(dev)
-
-    def u8(nbytes):
-        return torch.zeros(max(int(nbytes), 16), dtype=torch.uint8, device=dev)
-
     stream = torch.cuda.current_stream(dev)
     with ctx.on_stream(stream.cuda_stream):
-        d_data = up(np.frombuffer(bytes(data), np.uint8))
-        d_size, d_off = up(sizes), u8(8 * n)
-        _lib.check(L.nkv_record_offsets_dev(ctx.h, d_size.data_ptr(), n, d_off.data_ptr()))
-        d_nodes, d_crc, d_stats = u8(L.nkv_total_nodes(n) * 20), u8(4 * n), u8(24)
-        _lib.check(L.nkv_tree_verify_records_dev(ctx.h, d_data.data_ptr(), nbytes, d_off.data_ptr(), n,
-                                                 d_nodes.data_ptr(), d_crc.data_ptr(), d_stats.data_ptr()),
-                   "flush read")
-        bad, first, hdr = d_stats.cpu().numpy().view(np.uint64).tolist()
-        if hdr:
-            raise _lib.NkvError(_lib.NKV_ERR_INVALID, "flush read")
-        if bad:
-            got = int(d_crc.cpu().numpy().view(np.uint32)[first])
-            stored = int(np.frombuffer(bytes(data), "<u4", 1, int(sizes[:first].sum()))[0])
-            raise ValueError(f"Bad Record checksum (got {got}, expected {stored})")
+        d_data, d_off = _checked_upload(ctx, dev, data, sizes, "flush read")
         return _flush_tail(ctx, dev_index, stream, d_data, nbytes, d_off, n, seed, false_positive_rate,
                            summary_page_size, resident)
 
@@ -401,11 +385,7 @@ def _flush_tail(ctx, dev_index, stream, d_log, nbytes, d_off, n, seed, false_pos
     import torch
     from . import _lib
     dev = torch.device("cuda", dev_index)
-
-    def u8(nbytes):
-        return torch.zeros(max(int(nbytes), 16), dtype=torch.uint8, device=dev)
-
-    d_out, d_out_off, d_out_src = u8(nbytes), u8(8 * n), u8(8 * n)
+    d_out, d_out_off, d_out_src = u8(dev, nbytes), u8(dev, 8 * n), u8(dev, 8 * n)
     n_out, out_len = ctypes.c_uint64(0), ctypes.c_uint64(0)
     _lib.check(_lib.lib().nkv_sort_records_dev(ctx.h, d_log.data_ptr(), nbytes, d_off.data_ptr(), n,
                                                d_out.data_ptr(), nbytes, d_out_off.data_ptr(), d_out_src.data_ptr(),
@@ -446,20 +426,14 @@ def recover(segments, device=None, **flush_kwargs):
     L = _lib.lib()
     dev = torch.device("cuda", dev_index)
 
-    def up(a):
-        return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).copy()).to(dev)
-
-    def u8(nb):
-        return torch.zeros(max(int(nb), 16), dtype=torch.uint8, device=dev)
-
     def u64(t, count):
         return t.cpu().numpy().view(np.uint64)[:count].copy()
 
     stream = torch.cuda.current_stream(dev)
     with ctx.on_stream(stream.cuda_stream):
-        d_data, d_seg = up(np.frombuffer(data, np.uint8)), up(seg_off)
+        d_data, d_seg = up(dev, np.frombuffer(data, np.uint8)), up(dev, seg_off)
         cap = nbytes // 30
-        d_off, d_first, d_len = u8(8 * cap), u8(8 * (S + 1)), u8(8 * S)
+        d_off, d_first, d_len = u8(dev, 8 * cap), u8(dev, 8 * (S + 1)), u8(dev, 8 * S)
         n_out, stats = ctypes.c_uint64(0), (ctypes.c_uint64 * 4)()
         _lib.check(L.nkv_frame_records_dev(ctx.h, d_data.data_ptr(), nbytes, d_seg.data_ptr(), S, 0,
                                            d_off.data_ptr(), cap, d_first.data_ptr(), d_len.data_ptr(),
@@ -481,9 +455,9 @@ def recover(segments, device=None, **flush_kwargs):
                 data = wal.close_gaps(data, seg_off, seg_len)
                 log_len = len(data)
                 assert log_len == framed
-                d_data = up(np.frombuffer(data, np.uint8))
-                d_off = up(off)
-        d_crc, d_stats = u8(4 * n), u8(24)
+                d_data = up(dev, np.frombuffer(data, np.uint8))
+                d_off = up(dev, off)
+        d_crc, d_stats = u8(dev, 4 * n), u8(dev, 24)
         _lib.check(L.nkv_record_crc_dev(ctx.h, d_data.data_ptr(), log_len, d_off.data_ptr(), n, d_crc.data_ptr(),
                                         d_stats.data_ptr()), "WAL replay: checksums")
         bad, bad_first, hdr = d_stats.cpu().numpy().view(np.uint64)[:3].tolist()
@@ -525,18 +499,12 @@ def flush_puts(keys, values, timestamps=None, status=None, type_info=None, devic
     L = _lib.lib()
     dev = torch.device("cuda", dev_index)
 
-    def up(a):
-        if a is None:
-            return None
-        a = np.ascontiguousarray(a).view(np.uint8)
-        return torch.from_numpy(a.copy() if a.size else np.zeros(16, np.uint8)).to(dev)
-
     def ptr(t):
         return None if t is None else t.data_ptr()
 
     stream = torch.cuda.current_stream(dev)
     with ctx.on_stream(stream.cuda_stream):
-        d = {k: up(p[k]) for k in ("keys", "koff", "klen", "vals", "voff", "vlen", "ts", "status", "type")}
+        d = {k: up_opt(dev, p[k]) for k in ("keys", "koff", "klen", "vals", "voff", "vlen", "ts", "status", "type")}
         puts = _lib.NkvPuts(ptr(d["keys"]), p["keys"].size, ptr(d["koff"]), ptr(d["klen"]), ptr(d["vals"]),
                             p["vals"].size, ptr(d["voff"]), ptr(d["vlen"]), ptr(d["ts"]), p["ts_all"],
                             ptr(d["status"]), ptr(d["type"]), n)
@@ -591,10 +559,7 @@ def upload_table(table: Table, filter=None, device=None) -> ResidentTable:
     ctx = _lib.default_context(dev_index)
     dev = torch.device("cuda", dev_index)
 
-    def up(a):
-        return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).copy()).to(dev)
-
-    d_data, d_size = up(np.frombuffer(bytes(data) or b"\0", np.uint8)), up(sizes)
+    d_data, d_size = up(dev, np.frombuffer(bytes(data) or b"\0", np.uint8)), up(dev, sizes)
     d_off = torch.zeros(8 * n, dtype=torch.uint8, device=dev)
     stream = torch.cuda.current_stream(dev)
     with ctx.on_stream(stream.cuda_stream):
@@ -606,7 +571,7 @@ def upload_table(table: Table, filter=None, device=None) -> ResidentTable:
         words = np.zeros(((m + 31) // 32) * 4, np.uint8)
         contents = np.frombuffer(filter.Contents, np.uint8)
         words[:contents.size] = contents
-        d_bits = up(words)
+        d_bits = up(dev, words)
     return ResidentTable(dev_index, d_data, nbytes, d_off, n, d_bits, m, k, seed0)
 
 
@@ -653,18 +618,10 @@ def get_many(tables: Sequence[ResidentTable], keys: Sequence[bytes], device=None
     L = _lib.lib()
     dev = torch.device("cuda", dev_index)
 
-    def up(a):
-        return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).copy()).to(dev)
-
-    def u8(nbytes):
-        return torch.zeros(max(int(nbytes), 16), dtype=torch.uint8, device=dev)
-
-    keys = [bytes(k) for k in keys]
-    klen = np.fromiter((len(k) for k in keys), dtype=np.uint64, count=q)
-    koff = np.zeros(q, np.uint64)
-    koff[1:] = np.cumsum(klen[:-1])
-    d_keys, d_koff, d_klen = up(np.frombuffer(b"".join(keys) or b"\0", np.uint8)), up(koff), up(klen)
-    d_hit, d_status, d_stage, d_err, d_out_off = u8(8 * q), u8(q), u8(q * T), u8(4), u8(8 * (q + 1))
+    blob, koff, klen = pack_keys(keys)
+    d_keys, d_koff, d_klen = up(dev, np.frombuffer(blob, np.uint8)), up(dev, koff), up(dev, klen)
+    d_hit, d_status, d_stage, d_err = u8(dev, 8 * q), u8(dev, q), u8(dev, q * T), u8(dev, 4)
+    d_out_off = u8(dev, 8 * (q + 1))
     structs = [t.as_struct() for t in tables]
     tabs = (_lib.NkvLookupTable * max(T, 1))(*structs)
     with_mem = memtable is not None and memtable.n > 0  # an empty memtable holds no key
@@ -682,7 +639,7 @@ def get_many(tables: Sequence[ResidentTable], keys: Sequence[bytes], device=None
         if with_mem:
             memtable.find_dev(d_keys, d_koff, d_klen, q, d_hit, d_status, table_id=T, overlay=True)
         if _indexed:  # the disk tables under every resident answer, named TV, TV + 1, ..
-            located = _locate_under(ctx, L, _indexed, TV, d_keys, d_koff, d_klen, q, d_hit, d_status, u8)
+            located = _locate_under(ctx, L, dev, _indexed, TV, d_keys, d_koff, d_klen, q, d_hit, d_status)
         if TV == 0:
             if _indexed:
                 stream.synchronize()
@@ -694,7 +651,7 @@ def get_many(tables: Sequence[ResidentTable], keys: Sequence[bytes], device=None
                                            ctypes.byref(out_len)), "point lookup, Value sizes")
         if int(d_err.cpu().numpy().view(np.uint32)[0]):
             raise _lib.NkvError(_lib.NKV_ERR_INVALID, "point lookup: a record reaches outside its table")
-        d_out = u8(out_len.value)
+        d_out = u8(dev, out_len.value)
         _lib.check(L.nkv_lookup_values_dev(ctx.h, tabs, T, d_hit.data_ptr(), d_status.data_ptr(), q,
                                            d_out.data_ptr(), out_len.value, d_out_off.data_ptr(),
                                            ctypes.byref(out_len)), "point lookup, Values")
@@ -715,13 +672,13 @@ def get_many(tables: Sequence[ResidentTable], keys: Sequence[bytes], device=None
 # ---------------------------------------------------------------------------
 # tables whose Data file stays on disk (nkv_locate_dev over sstable.IndexedTable)
 
-def _locate_under(ctx, L, indexed, base, d_keys, d_koff, d_klen, q, d_hit, d_status, u8):
+def _locate_under(ctx, L, dev, indexed, base, d_keys, d_koff, d_klen, q, d_hit, d_status):
     """nkv_locate_dev with overlay over the answers in d_hit / d_status, the
     Index-only tables named base, base + 1, ..; in chunks of
     NKV_LOOKUP_MAX_TABLES, each laid under the ones before.  Returns the
     d_data_off tensor."""
     from . import _lib
-    d_data_off = u8(8 * q)
+    d_data_off = u8(dev, 8 * q)
     for t0 in range(0, len(indexed), _lib.NKV_LOOKUP_MAX_TABLES):
         part = indexed[t0:t0 + _lib.NKV_LOOKUP_MAX_TABLES]
         tabs = (_lib.NkvIndexTable * len(part))(*[t.as_struct() for t in part])
@@ -761,18 +718,9 @@ def locate_many(tables, keys: Sequence[bytes], stages: bool = False, base: int =
     ctx = _lib.default_context(dev_index)
     dev = torch.device("cuda", dev_index)
 
-    def up(a):
-        return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).copy()).to(dev)
-
-    def u8(nbytes):
-        return torch.zeros(max(int(nbytes), 16), dtype=torch.uint8, device=dev)
-
-    keys = [bytes(k) for k in keys]
-    klen = np.fromiter((len(k) for k in keys), dtype=np.uint64, count=q)
-    koff = np.zeros(q, np.uint64)
-    koff[1:] = np.cumsum(klen[:-1])
-    d_keys, d_koff, d_klen = up(np.frombuffer(b"".join(keys) or b"\0", np.uint8)), up(koff), up(klen)
-    d_hit, d_off, d_status, d_stage, d_err = u8(8 * q), u8(8 * q), u8(q), u8(q * T), u8(4)
+    blob, koff, klen = pack_keys(keys)
+    d_keys, d_koff, d_klen = up(dev, np.frombuffer(blob, np.uint8)), up(dev, koff), up(dev, klen)
+    d_hit, d_off, d_status, d_stage, d_err = u8(dev, 8 * q), u8(dev, 8 * q), u8(dev, q), u8(dev, q * T), u8(dev, 4)
     tabs = (_lib.NkvIndexTable * T)(*[t.as_struct() for t in tables])
     stream = torch.cuda.current_stream(dev)
     with ctx.on_stream(stream.cuda_stream):

@@ -23,6 +23,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib, record
+from ._dev import pack_keys, up, up_opt
 
 NONE = 2**64 - 1
 
@@ -59,13 +60,6 @@ class Memtable:
     def _stream(self):
         import torch
         return torch.cuda.current_stream(self._dev)
-
-    def _up(self, a):
-        import torch
-        if a is None:
-            return None
-        a = np.ascontiguousarray(a).view(np.uint8)
-        return torch.from_numpy(a.copy() if a.size else np.zeros(16, np.uint8)).to(self._dev)
 
     def _state(self) -> List[int]:
         return self.d_state.cpu().numpy().view(np.uint64).tolist()
@@ -134,7 +128,8 @@ class Memtable:
 
         stream = self._stream()
         with self._ctx.on_stream(stream.cuda_stream):
-            d = {k: self._up(p[k]) for k in ("keys", "koff", "klen", "vals", "voff", "vlen", "ts", "status", "type")}
+            d = {k: up_opt(self._dev, p[k])
+                 for k in ("keys", "koff", "klen", "vals", "voff", "vlen", "ts", "status", "type")}
             puts = _lib.NkvPuts(ptr(d["keys"]), p["keys"].size, ptr(d["koff"]), ptr(d["klen"]), ptr(d["vals"]),
                                 p["vals"].size, ptr(d["voff"]), ptr(d["vlen"]), ptr(d["ts"]), p["ts_all"],
                                 ptr(d["status"]), ptr(d["type"]), m)
@@ -183,17 +178,13 @@ class Memtable:
         """Memtable.Find per key: the Record of its latest write (a tombstone
         included), or None."""
         import torch
-        keys = [bytes(k) for k in keys]
         q = len(keys)
         if q == 0:
             return []
-        klen = np.fromiter((len(k) for k in keys), dtype=np.uint64, count=q)
-        koff = np.zeros(q, np.uint64)
-        koff[1:] = np.cumsum(klen[:-1])
+        blob, koff, klen = pack_keys(keys)
         stream = self._stream()
         with self._ctx.on_stream(stream.cuda_stream):
-            d_keys, d_koff, d_klen = self._up(np.frombuffer(b"".join(keys) or b"\0", np.uint8)), self._up(koff), \
-                self._up(klen)
+            d_keys, d_koff, d_klen = (up(self._dev, a) for a in (np.frombuffer(blob, np.uint8), koff, klen))
             d_hit = torch.zeros(8 * q, dtype=torch.uint8, device=self._dev)
             d_status = torch.zeros(q, dtype=torch.uint8, device=self._dev)
             self.find_dev(d_keys, d_koff, d_klen, q, d_hit, d_status)

@@ -30,6 +30,7 @@ from typing import Iterable, List, Optional
 import numpy as np
 
 from . import _lib
+from ._dev import u8, up
 from .merkletree import MerkleNode, MerkleTree, MerkleTreeError, New, NewLeaf
 from .record import Record
 
@@ -252,25 +253,21 @@ def make_table_secondaries_from_records(path: str, dbname: str, summary_page_siz
         _create(f_summary, summary)
         raise MerkleTreeError("cannot build Merkle Tree from 0 nodes")
 
-    def u8(count):
-        return torch.zeros(max(int(count), 16), dtype=torch.uint8, device=dev)
-
     ts = torch.cuda.current_stream(dev)
     with ctx.on_stream(ts.cuda_stream):
-        d_data = torch.from_numpy(data.copy()).to(dev)
-        d_size = torch.from_numpy(sizes.view(np.uint8).copy()).to(dev)
-        d_off = u8(8 * n)
+        d_data, d_size = up(dev, data), up(dev, sizes)
+        d_off = u8(dev, 8 * n)
         _lib.check(L.nkv_record_offsets_dev(ctx.h, d_size.data_ptr(), n, d_off.data_ptr()))
         d_index, d_summary = index_summary_dev(ctx, dev, d_data.data_ptr(), nbytes, d_off.data_ptr(), n,
                                                summary_page_size)
         bf = d_bits = None
         if seed is not None:
             bf = bloomfilter.New(n, false_positive_rate, seed=seed, ctx=ctx)
-            d_bits = u8(((bf.M + 31) // 32) * 4)
+            d_bits = u8(dev, ((bf.M + 31) // 32) * 4)
             _lib.check(L.nkv_bloom_insert_records_dev(ctx.h, d_data.data_ptr(), nbytes, d_off.data_ptr(), n, bf.M,
                                                       bf.K, bf.HashSeeds[0] if bf.K else 0, d_bits.data_ptr()),
                        "makeFilter")
-        d_nodes, d_img, d_err = u8(L.nkv_total_nodes(n) * 20), u8(L.nkv_bfs_size(n)), u8(4)
+        d_nodes, d_img, d_err = u8(dev, L.nkv_total_nodes(n) * 20), u8(dev, L.nkv_bfs_size(n)), u8(dev, 4)
         _lib.check(L.nkv_tree_from_records_dev(ctx.h, d_data.data_ptr(), nbytes, d_off.data_ptr(), n,
                                                d_nodes.data_ptr(), d_err.data_ptr()), "MakeTable")
         _lib.check(L.nkv_bfs_image_dev(ctx.h, d_nodes.data_ptr(), n, d_img.data_ptr()), "Serialize image")
@@ -326,10 +323,7 @@ def open_index(index_bytes, summary_bytes, filter=None, device: Optional[int] = 
     ctx = _lib.default_context(dev_index)
     dev = torch.device("cuda", dev_index)
 
-    def up(a):
-        return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).copy()).to(dev)
-
-    d_index, d_summary = up(np.frombuffer(index_bytes, np.uint8)), up(np.frombuffer(summary_bytes, np.uint8))
+    d_index, d_summary = up(dev, np.frombuffer(index_bytes, np.uint8)), up(dev, np.frombuffer(summary_bytes, np.uint8))
     cap = len(index_bytes) // 16
     d_ent = torch.empty(8 * max(cap, 1), dtype=torch.uint8, device=dev)
     n, s, verdict = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint32(0)
@@ -348,7 +342,7 @@ def open_index(index_bytes, summary_bytes, filter=None, device: Optional[int] = 
         words = np.zeros(((m + 31) // 32) * 4, np.uint8)
         contents = np.frombuffer(bytes(filter.Contents), np.uint8)
         words[:contents.size] = contents
-        d_bits = up(words)
+        d_bits = up(dev, words)
     return IndexedTable(dev_index, d_index, len(index_bytes), d_ent, n.value, s.value, d_bits, m, k, seed0)
 
 

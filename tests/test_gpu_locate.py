@@ -493,6 +493,55 @@ def test_locate_refuses_bad_arguments_and_q_0_writes_nothing(nkv, oracle):
         assert L.nkv_locate_dev(ctx.h, one, 1, 0, p, p, p, 1, 0, *out) == INVALID, fld
 
 
+@pytest.mark.parametrize("filtered", [False, True], ids=["no-filter", "filter"])
+@pytest.mark.parametrize("T", [1, 2])
+def test_lookup_and_locate_agree_over_written_tables(nkv, oracle, T, filtered):
+    """The two instantiations of the search layer's kernel over the same
+    tables: nkv_lookup_dev over written Data tables and nkv_locate_dev (overlay
+    0) over the Indexes sstable.index_summary_dev makes of them where they lie,
+    the same filters and the same query batch.  The stage arrays and the hit
+    words are the same; the statuses differ only as LIVE / TOMBSTONE against
+    LOCATED (a written Index holds no -1 Offset), and a LOCATED key's Data
+    offset is its record's."""
+    from nakevaleng_amd import sstable
+    from tests import test_gpu_lookup as tl
+    _lib, ctx = nkv
+    dev = _torch().device("cuda", 0)
+    seen = set()
+    for n in (1, 2, 3, 64):
+        tabs, pool, rng = tl.make_world(oracle, 0x1280 + 8 * n + T, (n,) * T,
+                                        kinds=("real", "tiny") if filtered else (None,))
+        data = tl.upload(nkv, tabs)
+        index = Up((_lib.NkvIndexTable * T)(), T)
+        for t, tab in enumerate(tabs):
+            s = data.structs[t]
+            d_index, d_summary = sstable.index_summary_dev(ctx, dev, s.stream, s.stream_len, s.rec_off, n, 3)
+            ctx.sync()
+            assert d_index.cpu().numpy().tobytes() == tab.index
+            d_ent = _dev(np.zeros(n, np.uint64))
+            gn, gs, v = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint32(0)
+            index_len = int(d_index.numel())
+            assert _lib.lib().nkv_index_open_dev(ctx.h, d_index.data_ptr(), index_len, d_summary.data_ptr(),
+                                                 d_summary.numel(), d_ent.data_ptr(), n, ctypes.byref(gn),
+                                                 ctypes.byref(gs), ctypes.byref(v)) == 0
+            assert (gn.value, v.value) == (n, 0)
+            index.structs[t] = _lib.NkvIndexTable(d_index.data_ptr(), index_len, d_ent.data_ptr(), n, s.bits, s.m,
+                                                  s.k, s.seed0)
+            index.keep += [d_index, d_ent]
+        held = [k for tab in tabs for k in tab.keys]
+        for q in (1, 64, 65):
+            queries = (held + tl.make_queries(rng, pool, q))[-q:] if q > 1 else [held[-1]]
+            got = tl.dev_lookup(nkv, data, queries)
+            rc, hit, off, status, stage, err = dev_locate(nkv, index, queries)
+            assert (got.rc, got.err, rc, err) == (0, 0, 0, 0)
+            assert stage == got.stage.tolist() and hit == got.hit.tolist()
+            assert [ref.LOCATED if s in (1, 2) else s for s in got.status.tolist()] == status
+            want_off = [-1 if h == ref.HIT_NONE else int(tabs[h >> 32].offsets[h & 0xFFFFFFFF]) for h in hit]
+            assert off == want_off
+            seen |= set(status)
+    assert seen == {ref.ABSENT, ref.LOCATED}  # hits and misses both occurred
+
+
 # ---------------------------------------------------------------------------
 # Python, end to end
 
