@@ -5,7 +5,6 @@ Bloom inserts (sstable.go:49-56) for 1 Mi records of TotalSize 4096 whose
 (M = 10,050,663 bits, K = 7).  HIP events on the library's stream; prints one
 JSON line with keys/s, the kernel time, and the C oracle on one core."""
 import argparse
-import json
 import os
 import sys
 import time
@@ -16,6 +15,7 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
+import benchlib  # noqa: E402
 from nakevaleng_amd import _lib, bloomfilter  # noqa: E402
 
 
@@ -30,10 +30,7 @@ def main():
     ap.add_argument("--path", type=int, default=-1, help="NKV_OPT_BLOOM_PATH override")
     args = ap.parse_args()
     n, rb, ks = args.records, args.rec_bytes, args.key_bytes
-    L = _lib.lib()
-    ctx = _lib.Context(0)
-    s = torch.cuda.current_stream()
-    ctx.set_stream(s.cuda_stream)
+    L, ctx, s = benchlib.open_ctx()
     if args.path >= 0:
         ctx.set_option(_lib.NKV_OPT_BLOOM_PATH, args.path)
     m, k = bloomfilter.params(n, 0.01)
@@ -47,16 +44,7 @@ def main():
     def run():
         _lib.check(L.nkv_bloom_insert_dev(ctx.h, data.data_ptr(), off.data_ptr(), ln.data_ptr(), n, m, k, seed0,
                                           bits.data_ptr()))
-    for _ in range(args.warmup):
-        run()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record(s)
-    for _ in range(args.steps):
-        run()
-    e1.record(s)
-    torch.cuda.synchronize()
-    ms = e0.elapsed_time(e1) / args.steps
+    ms = benchlib.batch_ms(s, run, args.warmup, args.steps)
     out = {"metric": "SSTable filter build (murmur3 Bloom inserts), keys/s", "value": round(n / (ms * 1e-3), 1),
            "unit": "keys/s", "ms_per_launch": round(ms, 4), "keys": n, "key_bytes": ks, "m_bits": m, "k": k,
            "bit_updates_per_s": round(n * k / (ms * 1e-3), 1)}
@@ -74,7 +62,7 @@ def main():
         hk = data.view(n, rb)[:, 30:30 + ks].cpu().numpy().reshape(-1).copy()
         want = oc.bloom_insert(hk, np.arange(n, dtype=np.uint64) * ks, np.full(n, ks, np.uint64), m, k, seed0)
         out["verified_vs_oracle"] = bool(np.array_equal(bits.cpu().numpy()[:want.size], want))
-    print(json.dumps(out), flush=True)
+    benchlib.line(out)
     ctx.close()
 
 

@@ -9,7 +9,6 @@ HIP events on the library's stream, the HBM roofline fraction, and the C
 oracle's single-thread rate on a bounded sample.
 """
 import argparse
-import json
 import os
 import sys
 import time
@@ -20,6 +19,7 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
+import benchlib  # noqa: E402
 from nakevaleng_amd import _lib  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0
@@ -37,17 +37,11 @@ def main():
     args = ap.parse_args()
     n, rb, ks = args.records, args.rec_bytes, args.key_bytes
     vs = rb - 30 - ks
-    L = _lib.lib()
-    ctx = _lib.Context(0)
-    s = torch.cuda.current_stream()
-    ctx.set_stream(s.cuda_stream)
+    L, ctx, s = benchlib.open_ctx()
     if args.crc_load >= 0:
         ctx.set_option(_lib.NKV_OPT_CRC_LOAD, args.crc_load)
-    data = torch.empty(n * rb, dtype=torch.uint8, device="cuda")
-    _lib.check(L.nkv_fill_splitmix64_dev(ctx.h, data.data_ptr(), n * rb, 0x6E616B65))
+    data = benchlib.device_log(ctx, n, ks, vs)
     v = data.view(n, rb)
-    v[:, 14:22] = torch.from_numpy(np.frombuffer(np.uint64(ks).tobytes(), np.uint8).copy()).cuda()
-    v[:, 22:30] = torch.from_numpy(np.frombuffer(np.uint64(vs).tobytes(), np.uint8).copy()).cuda()
     off = torch.arange(n, dtype=torch.int64, device="cuda") * rb
     crc = torch.empty(n * 4, dtype=torch.uint8, device="cuda")
     stats = torch.empty(24, dtype=torch.uint8, device="cuda")
@@ -58,16 +52,7 @@ def main():
     run()
     torch.cuda.synchronize()
     v[:, 0:4] = crc.view(n, 4)  # store the checksums: every record must now verify
-    for _ in range(args.warmup):
-        run()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record(s)
-    for _ in range(args.steps):
-        run()
-    e1.record(s)
-    torch.cuda.synchronize()
-    ms = e0.elapsed_time(e1) / args.steps
+    ms = benchlib.batch_ms(s, run, args.warmup, args.steps)
     st = stats.cpu().numpy().view(np.uint64).tolist()
     span_bytes = n * (ks + vs)
     gbs = span_bytes / (ms * 1e-3) / 1e9
@@ -88,7 +73,7 @@ def main():
     if args.verify:
         out["verified_vs_oracle"] = bool(bad == 0 and np.array_equal(hc, crc.view(n, 4)[:sample].cpu().numpy()
                                                                        .reshape(-1).view(np.uint32)))
-    print(json.dumps(out), flush=True)
+    benchlib.line(out)
     ctx.close()
 
 

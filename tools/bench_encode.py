@@ -31,9 +31,7 @@ nakevaleng_amd/record.py on a small ragged batch first.
 """
 import argparse
 import ctypes
-import json
 import os
-import subprocess
 import sys
 import time
 
@@ -42,6 +40,7 @@ sys.path.insert(0, ROOT)
 
 import numpy as np  # noqa: E402
 
+import benchlib  # noqa: E402
 from tests.far import RAGGED  # noqa: E402
 
 SHAPES = {"a": 1 << 20, "b": 1 << 18, "r": 1 << 18}
@@ -58,18 +57,11 @@ def lengths(name):
     return (i % 34).astype(np.uint64), np.asarray(RAGGED, np.uint64)[i % len(RAGGED)]
 
 
-def build_cpu_encode():
-    src = os.path.join(ROOT, "tools", "cpu_encode.cpp")
-    so = os.path.join(ROOT, "build", "cpu_encode.so")
-    if not os.path.exists(so) or os.path.getmtime(so) < os.path.getmtime(src):
-        os.makedirs(os.path.dirname(so), exist_ok=True)
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-pthread", src, "-lz", "-o", so])
-    lib = ctypes.CDLL(so)
-    lib.cpu_encode.restype = ctypes.c_double
-    lib.cpu_encode.argtypes = [ctypes.c_void_p] * 7 + [ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
-                                                       ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p,
-                                                       ctypes.POINTER(ctypes.c_uint64)]
-    return lib
+def cpu_lib():
+    vp = ctypes.c_void_p
+    return benchlib.build_cpu("encode", {"cpu_encode": (ctypes.c_double, [vp] * 7 + [
+        ctypes.c_int64, vp, vp, ctypes.c_uint64, ctypes.c_int, vp, ctypes.POINTER(ctypes.c_uint64)])},
+        ["-pthread", "-lz"])
 
 
 def cpu_encode(cpu, kb, koff, klen, vb, voff, vlen, ts, status, type_info, threads, out):
@@ -117,10 +109,7 @@ def run_shape(name, args, cpu):
     kbytes, vbytes = int(klen.sum()), int(vlen.sum())
     total = 30 * n + kbytes + vbytes
     ts = (1_700_000_000 + np.arange(n) // 1000).astype(np.int64)
-    L = _lib.lib()
-    ctx = _lib.Context(0)
-    s = torch.cuda.current_stream()
-    ctx.set_stream(s.cuda_stream)
+    L, ctx, s = benchlib.open_ctx()
 
     def up(a):
         return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).copy()).cuda()
@@ -169,70 +158,30 @@ def run_shape(name, args, cpu):
         out["cpu_threads_agree"] = bool(np.array_equal(h_out16, h_out))
         del h_out, h_out16
 
-    for _ in range(args.warmup):
-        call()
-    ctx.set_timing(True)
-    call_ms, prep_ms, red_ms = [], [], []
-    for _ in range(args.steps):
-        t0 = time.perf_counter()
-        call()
-        call_ms.append((time.perf_counter() - t0) * 1e3)
-        a, b = ctx.last_timing()
-        prep_ms.append(a)
-        red_ms.append(b)
-    ctx.set_timing(False)
+    call_ms, prep_ms, red_ms = benchlib.phase_ms(ctx, call, args.warmup, args.steps)
 
     # the checksum launch alone, and the comparator: hipMemcpyDtoDAsync of out_len bytes
-    hip = ctypes.CDLL("libamdhip64.so.7")
-    hip.hipMemcpyDtoDAsync.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
     d_cmp = torch.empty(total, dtype=torch.uint8, device="cuda")
     d_crc2 = torch.empty(4 * n, dtype=torch.uint8, device="cuda")
-
-    def timed(launch):
-        ms = []
-        for it in range(args.warmup + args.steps):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(s)
-            launch()
-            e1.record(s)
-            torch.cuda.synchronize()
-            if it >= args.warmup:
-                ms.append(e0.elapsed_time(e1))
-        return ms
-
-    crc_ms = timed(lambda: _lib.check(L.nkv_crc32_dev(ctx.h, d_out.data_ptr() + 30, d_off.data_ptr(),
-                                                      d_plen.data_ptr(), n, d_crc2.data_ptr())))
+    crc_ms = benchlib.event_ms(s, lambda: _lib.check(L.nkv_crc32_dev(ctx.h, d_out.data_ptr() + 30, d_off.data_ptr(),
+                                                                     d_plen.data_ptr(), n, d_crc2.data_ptr())),
+                               args.warmup, args.steps)
     if not torch.equal(d_crc2, d_crc):
         raise SystemExit(f"bench_encode: shape {name}: the separate checksum launch differs from d_crc")
+    memcpy_ms = benchlib.memcpy_ms(s, d_cmp, d_out, total, args.warmup, args.steps)
 
-    def memcpy():
-        rc = hip.hipMemcpyDtoDAsync(d_cmp.data_ptr(), d_out.data_ptr(), total, s.cuda_stream)
-        if rc != 0:
-            raise RuntimeError(f"hipMemcpyDtoDAsync -> {rc}")
-
-    memcpy_ms = timed(memcpy)
-
-    med = lambda x: float(np.median(x))  # noqa: E731
-    mm = lambda x: [round(min(x), 3), round(max(x), 3)]  # noqa: E731
-    write_ms = med(red_ms) - med(crc_ms)
+    call_med = benchlib.put(out, "call_ms", call_ms, 3)
+    benchlib.put(out, "prepare_ms", prep_ms, 3)
+    red, crc = benchlib.put(out, "reduce_ms", red_ms, 3), benchlib.put(out, "crc_ms", crc_ms, 3)
+    write_ms = red - crc
     write_gbs = (kbytes + vbytes + total) / (write_ms * 1e-3) / 1e9
-    memcpy_gbs = 2 * total / (med(memcpy_ms) * 1e-3) / 1e9
-    out.update({"call_ms": round(med(call_ms), 3), "prepare_ms": round(med(prep_ms), 3),
-                "reduce_ms": round(med(red_ms), 3), "crc_ms": round(med(crc_ms), 3), "write_ms": round(write_ms, 3),
-                "write_gbs": round(write_gbs, 1), "memcpy_ms": round(med(memcpy_ms), 3),
-                "memcpy_gbs": round(memcpy_gbs, 1), "write_vs_memcpy": round(write_gbs / memcpy_gbs, 3),
-                "crc_gbs": round((kbytes + vbytes) / (med(crc_ms) * 1e-3) / 1e9, 1),
-                "call_ms_min_max": mm(call_ms), "prepare_ms_min_max": mm(prep_ms), "reduce_ms_min_max": mm(red_ms),
-                "crc_ms_min_max": mm(crc_ms), "memcpy_ms_min_max": mm(memcpy_ms)})
+    memcpy_gbs = 2 * total / (benchlib.put(out, "memcpy_ms", memcpy_ms, 3) * 1e-3) / 1e9
+    out.update({"write_ms": round(write_ms, 3), "write_gbs": round(write_gbs, 1), "memcpy_gbs": round(memcpy_gbs, 1),
+                "write_vs_memcpy": round(write_gbs / memcpy_gbs, 3),
+                "crc_gbs": round((kbytes + vbytes) / (crc * 1e-3) / 1e9, 1)})
     if "cpu_encode_s" in out:
-        out["call_speedup_vs_cpu"] = {k: round(v * 1e3 / med(call_ms), 1) for k, v in out["cpu_encode_s"].items()}
-    try:  # the shader clock the box reports right after the timed loops (read only)
-        import re
-        smi = subprocess.run(["rocm-smi", "--showclocks"], capture_output=True, text=True, timeout=30).stdout
-        m = re.search(r"sclk.*?\((\d+)Mhz\)", smi)
-        out["sclk_mhz_after"] = int(m.group(1)) if m else None
-    except Exception:
-        out["sclk_mhz_after"] = None
+        out["call_speedup_vs_cpu"] = {k: round(v * 1e3 / call_med, 1) for k, v in out["cpu_encode_s"].items()}
+    out["sclk_mhz_after"] = benchlib.sclk()  # right after the timed loops
     del d_cmp, got
     ctx.close()
 
@@ -250,11 +199,11 @@ def run_shape(name, args, cpu):
                 flush_ms.append((time.perf_counter() - t0) * 1e3)
             flushed = len(res["table"][1])
             del res
-        out["flush_puts_ms"] = round(med(flush_ms), 1)
-        out["flush_puts_ms_min_max"] = mm(flush_ms)
+        out["flush_puts_ms"] = round(benchlib.median(flush_ms), 1)  # its range keeps 3 digits
+        out["flush_puts_ms_min_max"] = [round(min(flush_ms), 3), round(max(flush_ms), 3)]
         out["flush_puts_calls"] = args.flush_steps
         out["flushed_records"] = flushed
-    print(json.dumps(out), flush=True)
+    benchlib.line(out)
     del d_out, d_keys, d_vals
     torch.cuda.empty_cache()
     return out
@@ -273,14 +222,10 @@ def main():
         print("bench_encode: fewer than 20 timed calls: the medians are not for the record", file=sys.stderr)
     cpu = None
     if not args.no_cpu:
-        cpu = build_cpu_encode()
+        cpu = cpu_lib()
         check_cpu_encode(cpu)
     results = [run_shape(name, args, cpu) for name in args.shapes.split(",")]
-    out = {"metric": "record encode on the device", "shapes": results}
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        json.dump(out, f, indent=1)
-        f.write("\n")
+    benchlib.write({"metric": "record encode on the device", "shapes": results}, args.out)
 
 
 if __name__ == "__main__":

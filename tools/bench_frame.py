@@ -27,10 +27,7 @@ paths: the measurement behind the auto rule's mean-segment threshold.
 """
 import argparse
 import ctypes
-import json
 import os
-import statistics
-import subprocess
 import sys
 import time
 
@@ -39,41 +36,32 @@ sys.path.insert(0, ROOT)
 
 import numpy as np  # noqa: E402
 
+import benchlib  # noqa: E402
+
 N = 1 << 20
 SEED = 0x6672616D
 
 
-def build_cpu_frame():
-    src = os.path.join(ROOT, "tools", "cpu_frame.cpp")
-    so = os.path.join(ROOT, "build", "cpu_frame.so")
-    if not os.path.exists(so) or os.path.getmtime(so) < os.path.getmtime(src):
-        os.makedirs(os.path.dirname(so), exist_ok=True)
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", src, "-o", so])
-    lib = ctypes.CDLL(so)
-    lib.cpu_frame.restype = ctypes.c_uint64
-    lib.cpu_frame.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
-                              ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_uint64)]
-    return lib
+def cpu_lib():
+    vp, u64 = ctypes.c_void_p, ctypes.c_uint64
+    return benchlib.build_cpu("frame", {"cpu_frame": (u64, [vp, u64, vp, u64, vp, ctypes.POINTER(ctypes.c_double),
+                                                           ctypes.POINTER(u64)])})
 
 
 def make_table(ctx, n, rec, zeros=False):
     """n records of rec bytes with 16-byte keys on the device: the fill's bytes, the size fields set."""
     import torch
-    from nakevaleng_amd import _lib
-    buf = torch.empty(n * rec, dtype=torch.uint8, device="cuda")
-    _lib.check(_lib.lib().nkv_fill_splitmix64_dev(ctx.h, buf.data_ptr(), n * rec, SEED))
-    ctx.sync()
-    tab = buf.view(n, rec)
+    buf = benchlib.device_log(ctx, n, 16, rec - 46, seed=SEED)
     if zeros:
-        tab[:, 46:] = 0
-    sizes = np.frombuffer(np.asarray([16, rec - 46], np.uint64).tobytes(), np.uint8).copy()
-    tab[:, 14:30] = torch.from_numpy(sizes).cuda()
+        buf.view(n, rec)[:, 46:] = 0
     torch.cuda.synchronize()
     return buf
 
 
 def timed(call, args):
-    """(median ms, [min, max], results of the last call)."""
+    """(median ms, [min, max], results of the last call): the host clock around
+    a call that synchronizes, its own mode beside benchlib's loops because a
+    call slower than 1 s is timed --slow-steps times."""
     out = None
     for _ in range(args.warmup):
         t0 = time.perf_counter()
@@ -85,7 +73,7 @@ def timed(call, args):
         t0 = time.perf_counter()
         out = call()
         ms.append((time.perf_counter() - t0) * 1e3)
-    return round(statistics.median(ms), 3), [round(min(ms), 3), round(max(ms), 3)], out
+    return round(benchlib.median(ms), 3), [round(min(ms), 3), round(max(ms), 3)], out
 
 
 def run_paths(ctx, d_stream, nbytes, seg, want_off, args, paths=(1, 2, 0)):
@@ -171,7 +159,7 @@ def main():
     import torch
     from nakevaleng_amd import _lib, build as b
     b.build(quiet=True)
-    cpu = build_cpu_frame()
+    cpu = cpu_lib()
     ctx = _lib.Context(0)
     results = []
     shapes = {"t146": (N, 146, False, 0), "t4k": (N, 4096, False, 0), "wal": (N, 146, False, 5),
@@ -191,7 +179,7 @@ def main():
         if seg is None:
             r["m_over_n"] = round(candidates(d_stream, nbytes) / n, 3)
         results.append(r)
-        print(json.dumps(r), flush=True)
+        benchlib.line(r)
         if name == "t146" and args.sweep:
             sweep = []
             for per in (5, 20, 50, 100, 200, 500, 1000, 2000, 5000, 20000, 100000, N):
@@ -199,13 +187,11 @@ def main():
                 row = {"records_per_segment": per, "mean_segment_bytes": per * rec}
                 row.update(run_paths(ctx, d_stream, nbytes, seg, want, args, paths=(1, 2)))
                 sweep.append(row)
-                print(json.dumps(row), flush=True)
+                benchlib.line(row)
             results.append({"segment_sweep": sweep})
         del d_stream, host
         torch.cuda.empty_cache()
-    os.makedirs(os.path.dirname(args.out), exist_ok=True)
-    with open(args.out, "w") as f:
-        json.dump(results, f, indent=1)
+    benchlib.write(results, args.out)
     ctx.close()
 
 

@@ -24,12 +24,8 @@ table with tests/sstable_ref's restatement of the reference.
 """
 import argparse
 import ctypes
-import json
 import os
-import re
-import subprocess
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -37,44 +33,23 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
+import benchlib  # noqa: E402
 from nakevaleng_amd import _lib  # noqa: E402
 
 KS = 16
 SHAPES = [("1Mi x (16 B key, 4 KiB value)", 1 << 20, 4096), ("4Mi x (16 B key, 100 B value)", 1 << 22, 100)]
 
 
-def build_cpu_index():
-    src = os.path.join(ROOT, "tools", "cpu_index.cpp")
-    so = os.path.join(ROOT, "build", "cpu_index.so")
-    if not os.path.exists(so) or os.path.getmtime(so) < os.path.getmtime(src):
-        os.makedirs(os.path.dirname(so), exist_ok=True)
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", src, "-o", so])
-    lib = ctypes.CDLL(so)
-    lib.cpu_index.restype = ctypes.c_double
-    lib.cpu_index.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p,
-                              ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
-    return lib
+def cpu_lib():
+    vp, u64, pu64 = ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)
+    return benchlib.build_cpu("index", {"cpu_index": (ctypes.c_double, [vp, vp, u64, u64, vp, vp, pu64, pu64])})
 
 
-def sclk():
-    try:  # read only
-        smi = subprocess.run(["rocm-smi", "--showclocks"], capture_output=True, text=True, timeout=30).stdout
-        m = re.search(r"sclk.*?\((\d+)Mhz\)", smi)
-        return int(m.group(1)) if m else None
-    except Exception:
-        return None
-
-
-def one_shape(ctx, s, hip, name, n, vs, page, steps, warmup, cpu):
+def one_shape(L, ctx, s, name, n, vs, page, steps, warmup, cpu):
     from tests import sstable_ref as ref
-    L = _lib.lib()
     rb = 30 + KS + vs
     nbytes = n * rb
-    d = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
-    _lib.check(L.nkv_fill_splitmix64_dev(ctx.h, d.data_ptr(), nbytes, 0x696E6478 + vs))
-    v = d.view(n, rb)
-    v[:, 14:22] = torch.from_numpy(np.frombuffer(np.uint64(KS).tobytes(), np.uint8).copy()).cuda()
-    v[:, 22:30] = torch.from_numpy(np.frombuffer(np.uint64(vs).tobytes(), np.uint8).copy()).cuda()
+    d = benchlib.device_log(ctx, n, KS, vs, seed=0x696E6478 + vs)
     d_off = torch.arange(n, dtype=torch.int64, device="cuda") * rb
     ilen, slen = ctypes.c_uint64(0), ctypes.c_uint64(0)
     _lib.check(L.nkv_index_summary_dev(ctx.h, d.data_ptr(), nbytes, d_off.data_ptr(), n, page, None, 0, None, 0,
@@ -89,50 +64,23 @@ def one_shape(ctx, s, hip, name, n, vs, page, steps, warmup, cpu):
         torch.cuda.synchronize()
 
     torch.cuda.synchronize()
-    for _ in range(warmup):
-        call()
-    ctx.set_timing(True)
-    call_ms, measure_ms, writer_ms = [], [], []
-    for _ in range(steps):
-        t0 = time.perf_counter()
-        call()
-        call_ms.append((time.perf_counter() - t0) * 1e3)
-        a, b = ctx.last_timing()
-        measure_ms.append(a)
-        writer_ms.append(b)
-    ctx.set_timing(False)
+    call_ms, measure_ms, writer_ms = benchlib.phase_ms(ctx, call, warmup, steps)
 
     # the comparator: hipMemcpyDtoDAsync of as many bytes as the two images hold
     d_src = torch.empty(ni + ns, dtype=torch.uint8, device="cuda")
     d_dst = torch.empty(ni + ns, dtype=torch.uint8, device="cuda")
-    memcpy_ms = []
-    for it in range(warmup + steps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(s)
-        rc = hip.hipMemcpyDtoDAsync(d_dst.data_ptr(), d_src.data_ptr(), ni + ns, s.cuda_stream)
-        e1.record(s)
-        torch.cuda.synchronize()
-        if rc != 0:
-            raise RuntimeError(f"hipMemcpyDtoDAsync -> {rc}")
-        if it >= warmup:
-            memcpy_ms.append(e0.elapsed_time(e1))
-    clock = sclk()
+    memcpy_ms = benchlib.memcpy_ms(s, d_dst, d_src, ni + ns, warmup, steps)
+    clock = benchlib.sclk()
     del d_src, d_dst
 
-    med = lambda x: float(np.median(x))  # noqa: E731
-    writer_gbs = (ni + ns) / (med(writer_ms) * 1e-3) / 1e9
-    memcpy_gbs = (ni + ns) / (med(memcpy_ms) * 1e-3) / 1e9
     out = {"shape": name, "records": n, "key_bytes": KS, "value_bytes": vs, "stream_bytes": nbytes,
-           "index_len": ni, "summary_len": ns, "summary_entries": int(L.nkv_summary_entries(n, page)),
-           "call_ms": round(med(call_ms), 3), "call_ms_min_max": [round(min(call_ms), 3), round(max(call_ms), 3)],
-           "measure_ms": round(med(measure_ms), 3),
-           "writer_ms": round(med(writer_ms), 3),
-           "writer_ms_min_max": [round(min(writer_ms), 3), round(max(writer_ms), 3)],
-           "writer_gbs": round(writer_gbs, 1),
-           "memcpy_ms": round(med(memcpy_ms), 3),
-           "memcpy_ms_min_max": [round(min(memcpy_ms), 3), round(max(memcpy_ms), 3)],
-           "memcpy_gbs": round(memcpy_gbs, 1), "writer_vs_memcpy": round(writer_gbs / memcpy_gbs, 3),
-           "sclk_mhz_after": clock}
+           "index_len": ni, "summary_len": ns, "summary_entries": int(L.nkv_summary_entries(n, page))}
+    call_med = benchlib.put(out, "call_ms", call_ms, 3)
+    benchlib.put(out, "measure_ms", measure_ms, 3)
+    writer_gbs = (ni + ns) / (benchlib.put(out, "writer_ms", writer_ms, 3) * 1e-3) / 1e9
+    memcpy_gbs = (ni + ns) / (benchlib.put(out, "memcpy_ms", memcpy_ms, 3) * 1e-3) / 1e9
+    out.update({"writer_gbs": round(writer_gbs, 1), "memcpy_gbs": round(memcpy_gbs, 1),
+                "writer_vs_memcpy": round(writer_gbs / memcpy_gbs, 3), "sclk_mhz_after": clock})
 
     host = d.cpu().numpy()
     off = d_off.cpu().numpy().view(np.uint64)
@@ -157,7 +105,7 @@ def one_shape(ctx, s, hip, name, n, vs, page, steps, warmup, cpu):
     out["cpu_s"] = round(secs, 4)
     out["cpu_gbs_of_output"] = round((ni + ns) / secs / 1e9, 2)
     out["verified_vs_cpu_loop_and_restatement"] = True
-    out["call_speedup_vs_cpu"] = round(secs * 1e3 / med(call_ms), 1)
+    out["call_speedup_vs_cpu"] = round(secs * 1e3 / call_med, 1)
     return out
 
 
@@ -169,22 +117,13 @@ def main():
     ap.add_argument("--scale", type=int, default=1, help="divide the record counts (a quick look)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "index_bench.json"))
     args = ap.parse_args()
-    cpu = build_cpu_index()
-    ctx = _lib.Context(0)
-    s = torch.cuda.current_stream()
-    ctx.set_stream(s.cuda_stream)
-    hip = ctypes.CDLL("libamdhip64.so.7")
-    hip.hipMemcpyDtoDAsync.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    cpu = cpu_lib()
+    L, ctx, s = benchlib.open_ctx()
     out = {"metric": "SSTable Index and Summary tables on the device", "summary_page_size": args.page,
            "steps": args.steps, "shapes": []}
     for name, n, vs in SHAPES:
-        out["shapes"].append(one_shape(ctx, s, hip, name, n // args.scale, vs, args.page, args.steps, args.warmup,
-                                       cpu))
-    print(json.dumps(out), flush=True)
-    os.makedirs(os.path.dirname(args.out), exist_ok=True)
-    with open(args.out, "w") as f:
-        json.dump(out, f, indent=1)
-        f.write("\n")
+        out["shapes"].append(one_shape(L, ctx, s, name, n // args.scale, vs, args.page, args.steps, args.warmup, cpu))
+    benchlib.emit(out, args.out)
     ctx.close()
 
 

@@ -30,10 +30,7 @@ Prints one JSON line and writes it to profiles/locate_bench.json.
 """
 import argparse
 import ctypes
-import json
 import os
-import re
-import subprocess
 import sys
 import time
 
@@ -43,43 +40,20 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
+import benchlib  # noqa: E402
+from benchlib import keys_of  # noqa: E402
 from nakevaleng_amd import _lib  # noqa: E402
 
 KS, VS, T = 16, 100, 4
 RB = 30 + KS + VS  # 146
 EB = 16 + KS       # bytes per Index entry
-MIX = 0x9E3779B97F4A7C15
 
 
-def build_cpu():
-    src = os.path.join(ROOT, "tools", "cpu_locate.cpp")
-    so = os.path.join(ROOT, "build", "cpu_locate.so")
-    if not os.path.exists(so) or os.path.getmtime(so) < os.path.getmtime(src):
-        os.makedirs(os.path.dirname(so), exist_ok=True)
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-pthread", src, "-o", so])
-    lib = ctypes.CDLL(so)
-    vp, u64 = ctypes.c_void_p, ctypes.c_uint64
-    lib.cpu_index_walk.restype = ctypes.c_double
-    lib.cpu_index_walk.argtypes = [vp, u64, vp, u64, vp, vp, vp]
-    lib.cpu_locate.restype = ctypes.c_double
-    lib.cpu_locate.argtypes = [vp, vp, vp, ctypes.c_int, vp, vp, vp, u64, vp, vp, ctypes.c_int]
-    return lib
-
-
-def sclk():
-    try:  # read only
-        smi = subprocess.run(["rocm-smi", "--showclocks"], capture_output=True, text=True, timeout=30).stdout
-        m = re.search(r"sclk.*?\((\d+)Mhz\)", smi)
-        return int(m.group(1)) if m else None
-    except Exception:
-        return None
-
-
-def keys_of(u):
-    k = np.empty((u.size, KS), np.uint8)
-    k[:, :8] = u.astype(">u8").view(np.uint8).reshape(-1, 8)
-    k[:, 8:] = (u * np.uint64(MIX)).astype(">u8").view(np.uint8).reshape(-1, 8)
-    return k
+def cpu_lib():
+    vp, u64, dbl = ctypes.c_void_p, ctypes.c_uint64, ctypes.c_double
+    return benchlib.build_cpu("locate", {"cpu_index_walk": (dbl, [vp, u64, vp, u64, vp, vp, vp]),
+                                         "cpu_locate": (dbl, [vp, vp, vp, ctypes.c_int, vp, vp, vp, u64, vp, vp,
+                                                              ctypes.c_int])}, ["-pthread"])
 
 
 def entries(keys, field):
@@ -124,7 +98,7 @@ def time_open(L, ctx, d_index, d_summary, d_ent, n, s, path, chunk, steps, warmu
     ent = d_ent.cpu().numpy().view(np.uint64)[:n]
     if (gn.value, gs.value, v.value) != (n, s, 0) or not np.array_equal(ent, np.arange(n, dtype=np.uint64) * EB):
         raise SystemExit(f"bench_locate: open (path {path}, chunk {chunk}) differs from the images")
-    return round(float(np.median(ms)), 3)
+    return round(benchlib.median(ms), 3)
 
 
 def main():
@@ -140,18 +114,11 @@ def main():
     args = ap.parse_args()
     n = q = (1 << 20) // args.scale
     chunks = [int(c) for c in args.chunks.split(",")]
-    cpu = build_cpu()
-    L = _lib.lib()
-    ctx = _lib.Context(0)
-    s = torch.cuda.current_stream()
-    ctx.set_stream(s.cuda_stream)
+    cpu = cpu_lib()
+    L, ctx, s = benchlib.open_ctx()
     rng = np.random.default_rng(0x6C6F6361)
 
-    us = []
-    for _ in range(T):
-        u = np.unique(rng.integers(0, 2**63, n, dtype=np.uint64))
-        assert u.size == n, "a key was drawn twice: pick another seed"
-        us.append(u)
+    us = [benchlib.distinct_u64(rng, n) for _ in range(T)]
     keys = [keys_of(u) for u in us]
 
     # ---- open
@@ -182,7 +149,7 @@ def main():
                                               args.open_warmup),
                          "chunked_ms": time_open(L, ctx, d_index, d_summary, d_ent, m, sn, 2, 0, args.open_steps,
                                                  args.open_warmup)}
-    clock_open = sclk()
+    clock_open = benchlib.sclk()
 
     # ---- locate: the queries
     kind = rng.permutation(np.repeat(np.arange(4), q // 4))  # 0, 1: present; 2: passes the filters; 3: rejected
@@ -203,13 +170,7 @@ def main():
     rtabs, itabs, keep, h_index = (_lib.NkvLookupTable * T)(), (_lib.NkvIndexTable * T)(), [], []
     gn, gs, v = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint32(0)
     for t in range(T):
-        rec = np.zeros((n, RB), np.uint8)
-        rec[:, 4] = 7
-        rec[:, 14:22] = np.frombuffer(np.uint64(KS).tobytes(), np.uint8)
-        rec[:, 22:30] = np.frombuffer(np.uint64(VS).tobytes(), np.uint8)
-        rec[:, 30:30 + KS] = keys[t]
-        d_rec = dev(rec)
-        del rec
+        d_rec = dev(benchlib.host_records(keys[t], VS))
         d_bits = torch.zeros(((m.value + 31) // 32) * 4, dtype=torch.uint8, device="cuda")
         torch.cuda.synchronize()
         _lib.check(L.nkv_bloom_insert_records_dev(ctx.h, d_rec.data_ptr(), n * RB, d_off.data_ptr(), n, m.value,
@@ -246,17 +207,8 @@ def main():
                                     out2[2].data_ptr(), st2[1].data_ptr(), d_stage.data_ptr(), d_err.data_ptr()))
 
     # the two alternate call by call, so both see the same clocks
-    ms = {"locate": [], "lookup": []}
-    for it in range(args.warmup + args.steps):
-        for name, fn in (("locate", locate), ("lookup", lookup)):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(s)
-            fn()
-            e1.record(s)
-            torch.cuda.synchronize()
-            if it >= args.warmup:
-                ms[name].append(e0.elapsed_time(e1))
-    clock = sclk()
+    locate_ms, lookup_ms = benchlib.alternating_ms(s, (locate, lookup), args.warmup, args.steps)
+    clock = benchlib.sclk()
     locate()
     torch.cuda.synchronize()
 
@@ -279,28 +231,21 @@ def main():
     if not ok:
         raise SystemExit("bench_locate: the device's hits or Data offsets differ from the host's")
 
-    med = lambda x: float(np.median(x))  # noqa: E731
+    loc = {"tables": T, "queries": q, "filter_bits": m.value, "filter_hashes": k.value,
+           "index_bytes_per_table": int(n * EB), "data_bytes_per_table": int(n * RB),
+           "steps": args.steps, "warmup": args.warmup}
+    locate_med = benchlib.put(loc, "locate_ms", locate_ms, 3)
+    lookup_med = benchlib.put(loc, "lookup_ms", lookup_ms, 3)
+    loc.update({"locate_keys_per_s": round(q / (locate_med * 1e-3)),
+                "lookup_keys_per_s": round(q / (lookup_med * 1e-3)),
+                "locate_vs_lookup": round(lookup_med / locate_med, 3),
+                "cpu_threads": args.threads, "cpu_s": round(cpu_s, 4), "cpu_keys_per_s": round(q / cpu_s),
+                "locate_speedup_vs_cpu": round(cpu_s * 1e3 / locate_med, 1),
+                "sclk_mhz_after": clock, "verified_vs_host_search": True})
     out = {"metric": "Index/Summary readers on the device", "key_bytes": KS, "entries_per_table": n,
            "open": opens, "open_size_sweep_page_3": sweep, "open_steps": args.open_steps,
-           "sclk_mhz_after_open": clock_open,
-           "locate": {"tables": T, "queries": q, "filter_bits": m.value, "filter_hashes": k.value,
-                      "index_bytes_per_table": int(n * EB), "data_bytes_per_table": int(n * RB),
-                      "steps": args.steps, "warmup": args.warmup,
-                      "locate_ms": round(med(ms["locate"]), 3),
-                      "locate_ms_min_max": [round(min(ms["locate"]), 3), round(max(ms["locate"]), 3)],
-                      "lookup_ms": round(med(ms["lookup"]), 3),
-                      "lookup_ms_min_max": [round(min(ms["lookup"]), 3), round(max(ms["lookup"]), 3)],
-                      "locate_keys_per_s": round(q / (med(ms["locate"]) * 1e-3)),
-                      "lookup_keys_per_s": round(q / (med(ms["lookup"]) * 1e-3)),
-                      "locate_vs_lookup": round(med(ms["lookup"]) / med(ms["locate"]), 3),
-                      "cpu_threads": args.threads, "cpu_s": round(cpu_s, 4), "cpu_keys_per_s": round(q / cpu_s),
-                      "locate_speedup_vs_cpu": round(cpu_s * 1e3 / med(ms["locate"]), 1),
-                      "sclk_mhz_after": clock, "verified_vs_host_search": True}}
-    print(json.dumps(out), flush=True)
-    os.makedirs(os.path.dirname(args.out), exist_ok=True)
-    with open(args.out, "w") as f:
-        json.dump(out, f, indent=1)
-        f.write("\n")
+           "sclk_mhz_after_open": clock_open, "locate": loc}
+    benchlib.emit(out, args.out)
     ctx.close()
 
 

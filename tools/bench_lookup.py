@@ -38,12 +38,8 @@ and offsets with a numpy gather over the host copy of the tables.
 """
 import argparse
 import ctypes
-import json
 import os
-import re
-import subprocess
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -51,57 +47,19 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
+import benchlib  # noqa: E402
+from benchlib import keys_of  # noqa: E402
 from nakevaleng_amd import _lib  # noqa: E402
 
 KS, VS, T = 16, 100, 4
 RB = 30 + KS + VS
-MIX = 0x9E3779B97F4A7C15  # second key half = first half * MIX (mod 2^64)
 
 
-def build_cpu_lookup():
-    src = os.path.join(ROOT, "tools", "cpu_lookup.cpp")
-    so = os.path.join(ROOT, "build", "cpu_lookup.so")
-    if not os.path.exists(so) or os.path.getmtime(so) < os.path.getmtime(src):
-        os.makedirs(os.path.dirname(so), exist_ok=True)
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-pthread", src, "-o", so])
-    lib = ctypes.CDLL(so)
-    lib.cpu_lookup.restype = ctypes.c_double
-    lib.cpu_lookup.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
-                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_int]
-    return lib
-
-
-def sclk():
-    try:  # read only
-        smi = subprocess.run(["rocm-smi", "--showclocks"], capture_output=True, text=True, timeout=30).stdout
-        m = re.search(r"sclk.*?\((\d+)Mhz\)", smi)
-        return int(m.group(1)) if m else None
-    except Exception:
-        return None
-
-
-def keys_of(u):
-    """16-byte keys of the uint64 array u: u big-endian, then u * MIX big-endian
-    (ascending u = ascending key)."""
-    k = np.empty((u.size, KS), np.uint8)
-    k[:, :8] = u.astype(">u8").view(np.uint8).reshape(-1, 8)
-    k[:, 8:] = (u * np.uint64(MIX)).astype(">u8").view(np.uint8).reshape(-1, 8)
-    return k
-
-
-def host_table(rng, n):
-    """n records of strictly increasing keys, as record.Serialize lays them out
-    (the Crc field is left zero: the lookup does not read it)."""
-    u = np.unique(rng.integers(0, 2**63, n, dtype=np.uint64))
-    assert u.size == n, "a key was drawn twice: pick another seed"
-    rec = np.empty((n, RB), np.uint8)
-    rec[:, :30] = 0
-    rec[:, 4] = 7  # Timestamp
-    rec[:, 14:22] = np.frombuffer(np.uint64(KS).tobytes(), np.uint8)
-    rec[:, 22:30] = np.frombuffer(np.uint64(VS).tobytes(), np.uint8)
-    rec[:, 30:30 + KS] = keys_of(u)
-    rec[:, 30 + KS:] = np.frombuffer(rng.bytes(n * VS), np.uint8).reshape(n, VS)
-    return rec, u
+def cpu_lib():
+    vp = ctypes.c_void_p
+    return benchlib.build_cpu("lookup", {"cpu_lookup": (ctypes.c_double, [vp, vp, vp, ctypes.c_int, vp, vp, vp,
+                                                                          ctypes.c_uint64, vp, ctypes.c_int])},
+                              ["-pthread"])
 
 
 def main():
@@ -113,17 +71,12 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "lookup_bench.json"))
     args = ap.parse_args()
     n = q = (1 << 20) // args.scale
-    cpu = build_cpu_lookup()
-    L = _lib.lib()
-    ctx = _lib.Context(0)
-    s = torch.cuda.current_stream()
-    ctx.set_stream(s.cuda_stream)
-    hip = ctypes.CDLL("libamdhip64.so.7")
-    hip.hipMemcpyDtoDAsync.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    cpu = cpu_lib()
+    L, ctx, s = benchlib.open_ctx()
     rng = np.random.default_rng(0x6C6B7570)
 
     # the tables and the queries, on the host
-    recs, us = zip(*[host_table(rng, n) for _ in range(T)])
+    recs, us = zip(*[benchlib.host_table(rng, n, VS) for _ in range(T)])
     off = np.arange(n, dtype=np.uint64) * np.uint64(RB)
     kind = rng.permutation(np.repeat(np.arange(4), q // 4))  # 0, 1: present; 2: passes the filters; 3: rejected
     tq, jq = rng.integers(0, T, q), rng.integers(0, n, q)
@@ -166,16 +119,8 @@ def main():
         _lib.check(L.nkv_lookup_dev(ctx.h, tabs, T, d_keys.data_ptr(), d_koff.data_ptr(), d_klen.data_ptr(), q,
                                     d_hit.data_ptr(), d_status.data_ptr(), d_stage.data_ptr(), d_err.data_ptr()))
 
-    lookup_ms = []
-    for it in range(args.warmup + args.steps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(s)
-        lookup()
-        e1.record(s)
-        torch.cuda.synchronize()
-        if it >= args.warmup:
-            lookup_ms.append(e0.elapsed_time(e1))
-    clock_lookup = sclk()
+    lookup_ms = benchlib.event_ms(s, lookup, args.warmup, args.steps)
+    clock_lookup = benchlib.sclk()
 
     # the gather
     out_len = ctypes.c_uint64(0)
@@ -190,34 +135,13 @@ def main():
         _lib.check(L.nkv_lookup_values_dev(*vargs, d_out.data_ptr(), nb, d_out_off.data_ptr(), ctypes.byref(out_len)))
         torch.cuda.synchronize()
 
-    for _ in range(args.warmup):
-        gather()
-    ctx.set_timing(True)
-    call_ms, measure_ms, copy_ms = [], [], []
-    for _ in range(args.steps):
-        t0 = time.perf_counter()
-        gather()
-        call_ms.append((time.perf_counter() - t0) * 1e3)
-        a, b = ctx.last_timing()
-        measure_ms.append(a)
-        copy_ms.append(b)
-    ctx.set_timing(False)
+    call_ms, measure_ms, copy_ms = benchlib.phase_ms(ctx, gather, args.warmup, args.steps)
 
     # the comparator: hipMemcpyDtoDAsync of as many bytes as the gather writes
     d_src = torch.empty(nb, dtype=torch.uint8, device="cuda")
     d_dst = torch.empty(nb, dtype=torch.uint8, device="cuda")
-    memcpy_ms = []
-    for it in range(args.warmup + args.steps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(s)
-        rc = hip.hipMemcpyDtoDAsync(d_dst.data_ptr(), d_src.data_ptr(), nb, s.cuda_stream)
-        e1.record(s)
-        torch.cuda.synchronize()
-        if rc != 0:
-            raise RuntimeError(f"hipMemcpyDtoDAsync -> {rc}")
-        if it >= args.warmup:
-            memcpy_ms.append(e0.elapsed_time(e1))
-    clock = sclk()
+    memcpy_ms = benchlib.memcpy_ms(s, d_dst, d_src, nb, args.warmup, args.steps)
+    clock = benchlib.sclk()
     del d_src, d_dst
 
     # the host search over the same tables, and the checks
@@ -253,35 +177,26 @@ def main():
     if not ok:
         raise SystemExit("bench_lookup: the device's hits, stages or Values differ from the host's")
 
-    med = lambda x: float(np.median(x))  # noqa: E731
-    copy_gbs = nb / (med(copy_ms) * 1e-3) / 1e9
-    memcpy_gbs = nb / (med(memcpy_ms) * 1e-3) / 1e9
     out = {"metric": "batched point lookup over device-resident tables", "tables": T, "records_per_table": n,
            "key_bytes": KS, "value_bytes": VS, "queries": q, "filter_bits": m.value, "filter_hashes": k.value,
            "mix": {"present": int(present.sum()), "absent_in_range_passing_every_filter": int((kind == 2).sum()),
                    "absent_random": int((kind == 3).sum()),
                    "searched_to_index_per_table_of_the_passing": round(searched, 6),
                    "rejected_by_the_filter_per_table_of_the_random": round(rejected, 4)},
-           "steps": args.steps, "warmup": args.warmup,
-           "lookup_ms": round(med(lookup_ms), 3),
-           "lookup_ms_min_max": [round(min(lookup_ms), 3), round(max(lookup_ms), 3)],
-           "keys_per_s": round(q / (med(lookup_ms) * 1e-3)),
-           "cpu_threads": args.threads, "cpu_s": round(cpu_s, 4), "cpu_keys_per_s": round(q / cpu_s),
-           "lookup_speedup_vs_cpu": round(cpu_s * 1e3 / med(lookup_ms), 1),
-           "sclk_mhz_after_lookup": clock_lookup,
-           "gather_bytes": nb, "gather_call_ms": round(med(call_ms), 3),
-           "gather_call_ms_min_max": [round(min(call_ms), 3), round(max(call_ms), 3)],
-           "measure_ms": round(med(measure_ms), 3), "copy_ms": round(med(copy_ms), 3),
-           "copy_ms_min_max": [round(min(copy_ms), 3), round(max(copy_ms), 3)], "copy_gbs": round(copy_gbs, 1),
-           "memcpy_ms": round(med(memcpy_ms), 3),
-           "memcpy_ms_min_max": [round(min(memcpy_ms), 3), round(max(memcpy_ms), 3)],
-           "memcpy_gbs": round(memcpy_gbs, 1), "copy_vs_memcpy": round(copy_gbs / memcpy_gbs, 3),
-           "sclk_mhz_after": clock, "verified_vs_host_search_and_gather": True}
-    print(json.dumps(out), flush=True)
-    os.makedirs(os.path.dirname(args.out), exist_ok=True)
-    with open(args.out, "w") as f:
-        json.dump(out, f, indent=1)
-        f.write("\n")
+           "steps": args.steps, "warmup": args.warmup}
+    lookup_med = benchlib.put(out, "lookup_ms", lookup_ms, 3)
+    out.update({"keys_per_s": round(q / (lookup_med * 1e-3)),
+                "cpu_threads": args.threads, "cpu_s": round(cpu_s, 4), "cpu_keys_per_s": round(q / cpu_s),
+                "lookup_speedup_vs_cpu": round(cpu_s * 1e3 / lookup_med, 1),
+                "sclk_mhz_after_lookup": clock_lookup, "gather_bytes": nb})
+    benchlib.put(out, "gather_call_ms", call_ms, 3)
+    benchlib.put(out, "measure_ms", measure_ms, 3)
+    copy_gbs = nb / (benchlib.put(out, "copy_ms", copy_ms, 3) * 1e-3) / 1e9
+    memcpy_gbs = nb / (benchlib.put(out, "memcpy_ms", memcpy_ms, 3) * 1e-3) / 1e9
+    out.update({"copy_gbs": round(copy_gbs, 1), "memcpy_gbs": round(memcpy_gbs, 1),
+                "copy_vs_memcpy": round(copy_gbs / memcpy_gbs, 3),
+                "sclk_mhz_after": clock, "verified_vs_host_search_and_gather": True})
+    benchlib.emit(out, args.out)
     ctx.close()
 
 

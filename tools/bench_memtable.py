@@ -23,9 +23,7 @@ to a numpy result, and the host program's to the same.
 """
 import argparse
 import ctypes
-import json
 import os
-import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -33,24 +31,18 @@ sys.path.insert(0, ROOT)
 
 import numpy as np  # noqa: E402
 
+import benchlib  # noqa: E402
+
 N, KS, VS = 1 << 20, 16, 100
 RB = 30 + KS + VS
 MIXES = {"distinct": N, "sixteenth": N // 16, "single": 1}
 NONE = 2**64 - 1
 
 
-def build_cpu():
-    src = os.path.join(ROOT, "tools", "cpu_memtable.cpp")
-    so = os.path.join(ROOT, "build", "cpu_memtable.so")
-    if not os.path.exists(so) or os.path.getmtime(so) < os.path.getmtime(src):
-        os.makedirs(os.path.dirname(so), exist_ok=True)
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-pthread", src, "-o", so])
-    lib = ctypes.CDLL(so)
-    lib.cpu_memtable.restype = None
-    lib.cpu_memtable.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p,
-                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p,
-                                 ctypes.c_void_p, ctypes.c_void_p]
-    return lib
+def cpu_lib():
+    vp, u64 = ctypes.c_void_p, ctypes.c_uint64
+    return benchlib.build_cpu("memtable", {"cpu_memtable": (None, [vp, vp, u64, ctypes.c_int, vp, vp, vp, u64, vp, vp,
+                                                                   vp, vp])}, ["-pthread"])
 
 
 def host_answers(which, n):
@@ -69,23 +61,15 @@ def run_mix(name, args, cpu):
     n = args.records
     distinct = max(1, MIXES[name] * n // N)
     rng = np.random.default_rng(0x6D656D74 + len(name))
-    L = _lib.lib()
-    ctx = _lib.Context(0)
-    s = torch.cuda.current_stream()
-    ctx.set_stream(s.cuda_stream)
+    L, ctx, s = benchlib.open_ctx()
     uniq = rng.integers(0, 256, (distinct, KS), dtype=np.uint8)
     assert np.unique(uniq, axis=0).shape[0] == distinct
     which = np.arange(n) if distinct == n else rng.integers(0, distinct, n)
     distinct = int(np.unique(which).size)  # a uniform draw may miss a key
     keys = uniq[which]
     total = n * RB
-    d_log = torch.empty(total, dtype=torch.uint8, device="cuda")
-    _lib.check(L.nkv_fill_splitmix64_dev(ctx.h, d_log.data_ptr(), total, 0x6E616B65))
-    v = d_log.view(n, RB)
-    v[:, 12] = 0  # Status: all live
-    v[:, 14:22] = torch.from_numpy(np.frombuffer(np.uint64(KS).tobytes(), np.uint8).copy()).cuda()
-    v[:, 22:30] = torch.from_numpy(np.frombuffer(np.uint64(VS).tobytes(), np.uint8).copy()).cuda()
-    v[:, 30:30 + KS] = torch.from_numpy(keys).cuda()
+    d_log = benchlib.device_log(ctx, n, KS, VS, keys)
+    d_log.view(n, RB)[:, 12] = 0  # Status: all live
     d_roff = torch.arange(n, dtype=torch.int64, device="cuda") * RB
     slots = 2
     while slots < 2 * n:
@@ -146,26 +130,12 @@ def run_mix(name, args, cpu):
         raise SystemExit(f"bench_memtable: mix {name}: the flush kept {n_out.value} records, not {distinct}")
 
     def timed(fn, before=None):
-        ms = []
-        for it in range(args.warmup + args.steps):
-            if before:
-                before()
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(s)
-            fn()
-            e1.record(s)
-            torch.cuda.synchronize()
-            if it >= args.warmup:
-                ms.append(e0.elapsed_time(e1))
-        return ms
+        return benchlib.event_ms(s, fn, args.warmup, args.steps, before)
 
     t = {"add_ms": timed(add, clear), "find_ms": timed(find), "sort_ms": timed(sort), "lookup_ms": timed(lookup)}
-    med = {k: float(np.median(x)) for k, x in t.items()}
     out = {"mix": name, "records": n, "distinct_keys": distinct, "record_bytes": RB, "slots": slots,
            "steps": args.steps, "warmup": args.warmup, "verified_vs_host": True}
-    for k, x in t.items():
-        out[k] = round(med[k], 4)
-        out[k + "_min_max"] = [round(min(x), 4), round(max(x), 4)]
+    med = {k: benchlib.put(out, k, x, 4) for k, x in t.items()}
     out["add_mwrites_s"] = round(n / med["add_ms"] / 1e3, 1)
     out["find_mkeys_s"] = round(n / med["find_ms"] / 1e3, 1)
     out["sort_vs_add"] = round(med["sort_ms"] / med["add_ms"], 2)
@@ -192,7 +162,7 @@ def run_mix(name, args, cpu):
             out[f"cpu{threads}_find_ms"] = round(best[1] * 1e3, 3)
             out[f"cpu{threads}_vs_add"] = round(best[0] * 1e3 / med["add_ms"], 1)
             out[f"cpu{threads}_vs_find"] = round(best[1] * 1e3 / med["find_ms"], 1)
-    print(json.dumps(out), flush=True)
+    benchlib.line(out)
     ctx.close()
     return out
 
@@ -207,12 +177,9 @@ def main():
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "memtable_bench.json"))
     args = ap.parse_args()
-    cpu = None if args.no_cpu else build_cpu()
+    cpu = None if args.no_cpu else cpu_lib()
     results = [run_mix(name, args, cpu) for name in args.mixes.split(",")]
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        json.dump({"metric": "live memtable on the device", "mixes": results}, f, indent=1)
-        f.write("\n")
+    benchlib.write({"metric": "live memtable on the device", "mixes": results}, args.out)
 
 
 if __name__ == "__main__":

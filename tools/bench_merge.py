@@ -18,11 +18,8 @@ records against their input records.
 """
 import argparse
 import ctypes
-import json
 import os
-import subprocess
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -30,6 +27,7 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
+import benchlib  # noqa: E402
 from nakevaleng_amd import _lib  # noqa: E402
 from nakevaleng_amd.record import Record  # noqa: E402
 
@@ -37,17 +35,10 @@ KS, VS = 16, 4050
 RB = 30 + KS + VS
 
 
-def build_cpu_merge():
-    src = os.path.join(ROOT, "tools", "cpu_merge.cpp")
-    so = os.path.join(ROOT, "build", "cpu_merge.so")
-    if not os.path.exists(so) or os.path.getmtime(so) < os.path.getmtime(src):
-        os.makedirs(os.path.dirname(so), exist_ok=True)
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", src, "-o", so])
-    lib = ctypes.CDLL(so)
-    lib.cpu_merge.restype = ctypes.c_double
-    lib.cpu_merge.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_uint64), ctypes.c_int,
-                              ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
-    return lib
+def cpu_lib():
+    pu64 = ctypes.POINTER(ctypes.c_uint64)
+    return benchlib.build_cpu("merge", {"cpu_merge": (ctypes.c_double, [ctypes.POINTER(ctypes.c_void_p), pu64,
+                                                                        ctypes.c_int, ctypes.c_void_p, pu64, pu64])})
 
 
 def main():
@@ -62,10 +53,7 @@ def main():
     args = ap.parse_args()
     k, n = args.runs, args.records
     rng = np.random.default_rng(0x6D657267)
-    L = _lib.lib()
-    ctx = _lib.Context(0)
-    s = torch.cuda.current_stream()
-    ctx.set_stream(s.cuda_stream)
+    L, ctx, s = benchlib.open_ctx()
 
     pool = np.unique(rng.integers(0, 1 << 48, int(k * n * 0.8)).astype(np.uint64))
     ids, tss, d_runs = [], [], []
@@ -74,14 +62,10 @@ def main():
     for r in range(k):
         i = np.sort(rng.choice(pool, n, replace=False))
         t = rng.integers(0, 3, n).astype("<i8")
-        d = torch.empty(n * RB, dtype=torch.uint8, device="cuda")
-        _lib.check(L.nkv_fill_splitmix64_dev(ctx.h, d.data_ptr(), n * RB, 0x6E616B65 + r))
-        v = d.view(n, RB)
-        v[:, 4:12] = torch.from_numpy(t.view(np.uint8).reshape(n, 8).copy()).cuda()
-        v[:, 14:22] = torch.from_numpy(np.frombuffer(np.uint64(KS).tobytes(), np.uint8).copy()).cuda()
-        v[:, 22:30] = torch.from_numpy(np.frombuffer(np.uint64(VS).tobytes(), np.uint8).copy()).cuda()
-        v[:, 30:38] = torch.from_numpy(i.astype(">u8").view(np.uint8).reshape(n, 8).copy()).cuda()
-        v[:, 38:46] = 0
+        key = np.zeros((n, KS), np.uint8)
+        key[:, :8] = i.astype(">u8").view(np.uint8).reshape(n, 8)
+        d = benchlib.device_log(ctx, n, KS, VS, key, seed=benchlib.FILL_SEED + r)
+        d.view(n, RB)[:, 4:12] = torch.from_numpy(t.view(np.uint8).reshape(n, 8).copy()).cuda()
         ids.append(i)
         tss.append(t)
         d_runs.append(d)
@@ -97,35 +81,12 @@ def main():
                                            d_src.data_ptr(), ctypes.byref(n_out), ctypes.byref(out_len)))
 
     torch.cuda.synchronize()
-    for _ in range(args.warmup):
-        call()
-    ctx.set_timing(True)
-    call_ms, prep_ms, copy_ms = [], [], []
-    for _ in range(args.steps):
-        t0 = time.perf_counter()
-        call()
-        call_ms.append((time.perf_counter() - t0) * 1e3)
-        a, b = ctx.last_timing()
-        prep_ms.append(a)
-        copy_ms.append(b)
-    ctx.set_timing(False)
+    call_ms, prep_ms, copy_ms = benchlib.phase_ms(ctx, call, args.warmup, args.steps)
     nb, no = out_len.value, n_out.value
 
     # the comparator: hipMemcpyDtoDAsync of out_len bytes on the same stream
-    hip = ctypes.CDLL("libamdhip64.so.7")
-    hip.hipMemcpyDtoDAsync.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
     d_cmp = torch.empty(nb, dtype=torch.uint8, device="cuda")
-    memcpy_ms = []
-    for it in range(args.warmup + args.steps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(s)
-        rc = hip.hipMemcpyDtoDAsync(d_cmp.data_ptr(), d_out.data_ptr(), nb, s.cuda_stream)
-        e1.record(s)
-        torch.cuda.synchronize()
-        if rc != 0:
-            raise RuntimeError(f"hipMemcpyDtoDAsync -> {rc}")
-        if it >= args.warmup:
-            memcpy_ms.append(e0.elapsed_time(e1))
+    memcpy_ms = benchlib.memcpy_ms(s, d_cmp, d_out, nb, args.warmup, args.steps)
 
     # verify: every source against merge_closed (values left out: it reads keys and timestamps only)
     from tests.merge_ref import merge_closed
@@ -144,30 +105,20 @@ def main():
     if not ok:
         raise SystemExit("bench_merge: the device merge differs from merge_closed")
 
-    med = lambda x: float(np.median(x))  # noqa: E731
-    copy_gbs = 2 * nb / (med(copy_ms) * 1e-3) / 1e9
-    memcpy_gbs = 2 * nb / (med(memcpy_ms) * 1e-3) / 1e9
     out = {"metric": "compaction merge on the device", "runs": k, "records_per_run": n, "record_bytes": RB,
-           "n_out": no, "out_len": nb, "steps": args.steps,
-           "call_ms": round(med(call_ms), 3), "prepare_ms": round(med(prep_ms), 3),
-           "copy_ms": round(med(copy_ms), 3), "copy_gbs": round(copy_gbs, 1),
-           "memcpy_ms": round(med(memcpy_ms), 3), "memcpy_gbs": round(memcpy_gbs, 1),
-           "copy_vs_memcpy": round(copy_gbs / memcpy_gbs, 3),
-           "copy_ms_min_max": [round(min(copy_ms), 3), round(max(copy_ms), 3)],
-           "memcpy_ms_min_max": [round(min(memcpy_ms), 3), round(max(memcpy_ms), 3)],
-           "call_ms_min_max": [round(min(call_ms), 3), round(max(call_ms), 3)],
-           "call_gbs_of_output": round(nb / (med(call_ms) * 1e-3) / 1e9, 1),
-           "verified_vs_merge_closed": True, "verified_sample": min(args.sample, no) + 2}
-    try:  # the shader clock the box reports right after the timed loops (read only)
-        import re
-        smi = subprocess.run(["rocm-smi", "--showclocks"], capture_output=True, text=True, timeout=30).stdout
-        m = re.search(r"sclk.*?\((\d+)Mhz\)", smi)
-        out["sclk_mhz_after"] = int(m.group(1)) if m else None
-    except Exception:
-        out["sclk_mhz_after"] = None
+           "n_out": no, "out_len": nb, "steps": args.steps}
+    call_med = benchlib.put(out, "call_ms", call_ms, 3)
+    benchlib.put(out, "prepare_ms", prep_ms, 3)
+    copy_gbs = 2 * nb / (benchlib.put(out, "copy_ms", copy_ms, 3) * 1e-3) / 1e9
+    memcpy_gbs = 2 * nb / (benchlib.put(out, "memcpy_ms", memcpy_ms, 3) * 1e-3) / 1e9
+    out.update({"copy_gbs": round(copy_gbs, 1), "memcpy_gbs": round(memcpy_gbs, 1),
+                "copy_vs_memcpy": round(copy_gbs / memcpy_gbs, 3),
+                "call_gbs_of_output": round(nb / (call_med * 1e-3) / 1e9, 1),
+                "verified_vs_merge_closed": True, "verified_sample": min(args.sample, no) + 2,
+                "sclk_mhz_after": benchlib.sclk()})  # after the timed loops and the verification
 
     if not args.no_cpu:
-        cpu = build_cpu_merge()
+        cpu = cpu_lib()
         host = [d.cpu().numpy() for d in d_runs]
         h_out = np.empty(total, np.uint8)
         a, b = ctypes.c_uint64(0), ctypes.c_uint64(0)
@@ -181,12 +132,8 @@ def main():
         out["cpu_merge_s"] = round(secs, 3)
         out["cpu_merge_gbs_of_output"] = round(nb / secs / 1e9, 2)
         out["cpu_merge_agrees"] = bool(same)
-        out["call_speedup_vs_cpu"] = round(secs * 1e3 / med(call_ms), 1)
-    print(json.dumps(out), flush=True)
-    os.makedirs(os.path.dirname(args.out), exist_ok=True)
-    with open(args.out, "w") as f:
-        json.dump(out, f, indent=1)
-        f.write("\n")
+        out["call_speedup_vs_cpu"] = round(secs * 1e3 / call_med, 1)
+    benchlib.emit(out, args.out)
     ctx.close()
 
 

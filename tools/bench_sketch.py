@@ -30,15 +30,15 @@ paths 1 and 2 on packed 16-byte keys for n = 4 Ki .. 16 Mi, HLL at P = 4, 10,
 """
 import argparse
 import ctypes
-import json
 import os
-import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 import numpy as np  # noqa: E402
+
+import benchlib  # noqa: E402
 
 N = 1 << 20
 REC = 146
@@ -49,19 +49,11 @@ CPU_THREADS = 16
 GATE_HLL, GATE_CMS = 1.25, 2.0
 
 
-def build_cpu_sketch():
-    src = os.path.join(ROOT, "tools", "cpu_sketch.cpp")
-    so = os.path.join(ROOT, "build", "cpu_sketch.so")
-    if not os.path.exists(so) or os.path.getmtime(so) < os.path.getmtime(src):
-        os.makedirs(os.path.dirname(so), exist_ok=True)
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-pthread", src, "-o", so])
-    lib = ctypes.CDLL(so)
-    lib.cpu_hll.restype = ctypes.c_double
-    lib.cpu_hll.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
-    lib.cpu_cms.restype = ctypes.c_double
-    lib.cpu_cms.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
-                                                    ctypes.c_uint32, ctypes.c_int, ctypes.c_void_p]
-    return lib
+def cpu_lib():
+    vp, u32, dbl = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_double
+    return benchlib.build_cpu("sketch", {
+        "cpu_hll": (dbl, [vp] * 3 + [ctypes.c_uint64, ctypes.c_int, ctypes.c_int, vp]),
+        "cpu_cms": (dbl, [vp] * 3 + [ctypes.c_uint64, u32, u32, u32, ctypes.c_int, vp])}, ["-pthread"])
 
 
 def cpu_hll(cpu, base, off, ln, p, threads):
@@ -103,8 +95,7 @@ def make_shape(name):
         data = rng.integers(0, 256, N * 16, dtype=np.uint8)
         return data, np.arange(N, dtype=np.uint64) * 16, ln, False, None
     tab = rng.integers(0, 256, (N, REC), dtype=np.uint8)
-    tab[:, 14:22] = np.frombuffer(np.uint64(16).tobytes(), np.uint8)   # KeySize
-    tab[:, 22:30] = np.frombuffer(np.uint64(REC - 46).tobytes(), np.uint8)  # ValueSize
+    tab[:, 14:30] = benchlib.size_fields(16, REC - 46)
     if name == "d":
         tab[:, 30:46] = np.frombuffer(b"every key is one", np.uint8)
     rec_off = np.arange(N, dtype=np.uint64) * REC
@@ -114,10 +105,7 @@ def make_shape(name):
 def run_shape(name, args, cpu):
     import torch
     from nakevaleng_amd import _lib
-    L = _lib.lib()
-    ctx = _lib.Context(0)
-    s = torch.cuda.current_stream()
-    ctx.set_stream(s.cuda_stream)
+    L, ctx, s = benchlib.open_ctx()
     data, koff, klen, records, rec_off = make_shape(name)
 
     def up(a):
@@ -153,26 +141,14 @@ def run_shape(name, args, cpu):
         d_out = torch.zeros(out_bytes, dtype=torch.uint8, device="cuda")
         if path is not None:
             ctx.set_option(_lib.NKV_OPT_SKETCH_PATH, path)
-        ms = []
-        for it in range(args.warmup + args.steps):
-            d_out.zero_()
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(s)
-            _lib.check(call(d_out.data_ptr()))
-            e1.record(s)
-            torch.cuda.synchronize()
-            if it >= args.warmup:
-                ms.append(e0.elapsed_time(e1))
+        ms = benchlib.event_ms(s, lambda: _lib.check(call(d_out.data_ptr())), args.warmup, args.steps, d_out.zero_)
         ctx.set_option(_lib.NKV_OPT_SKETCH_PATH, 0)
         return ms, d_out.cpu().numpy()
 
-    med = lambda x: float(np.median(x))  # noqa: E731
     out = {"shape": name, "keys": N, "records_form": records, "steps": args.steps, "warmup": args.warmup}
 
     def put(key, ms):
-        out[key + "_ms"] = round(med(ms), 4)
-        out[key + "_ms_min_max"] = [round(min(ms), 4), round(max(ms), 4)]
-        return med(ms)
+        return benchlib.put(out, key + "_ms", ms, 4)
 
     # HLL
     want = None
@@ -217,7 +193,7 @@ def run_shape(name, args, cpu):
     out["cms_gate"] = GATE_CMS
     out["verified_vs_cpu_loop"] = cpu is not None
     ctx.close()
-    print(json.dumps(out), flush=True)
+    benchlib.line(out)
     del d_data, d_off, d_len
     torch.cuda.empty_cache()
     return out
@@ -231,10 +207,7 @@ SWEEP_TABLES = ((28, 3), (100, 33), (2719, 5), (1024, 16))
 def run_sweep():
     import torch
     from nakevaleng_amd import _lib
-    L = _lib.lib()
-    ctx = _lib.Context(0)
-    s = torch.cuda.current_stream()
-    ctx.set_stream(s.cuda_stream)
+    L, ctx, s = benchlib.open_ctx()
     nmax = max(SWEEP_N)
     d_keys = torch.empty(nmax * 16, dtype=torch.uint8, device="cuda")
     _lib.check(L.nkv_fill_splitmix64_dev(ctx.h, d_keys.data_ptr(), nmax * 16, 7))
@@ -246,18 +219,9 @@ def run_sweep():
     def timed(call, nbytes, path, steps=15, warm=3):
         d_out = torch.zeros(nbytes, dtype=torch.uint8, device="cuda")
         ctx.set_option(_lib.NKV_OPT_SKETCH_PATH, path)
-        ms = []
-        for it in range(warm + steps):
-            d_out.zero_()
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(s)
-            _lib.check(call(d_out.data_ptr()))
-            e1.record(s)
-            torch.cuda.synchronize()
-            if it >= warm:
-                ms.append(e0.elapsed_time(e1))
+        ms = benchlib.event_ms(s, lambda: _lib.check(call(d_out.data_ptr())), warm, steps, d_out.zero_)
         ctx.set_option(_lib.NKV_OPT_SKETCH_PATH, 0)
-        return round(float(np.median(ms)), 4)
+        return round(benchlib.median(ms), 4)
 
     rows = []
     for n in SWEEP_N:
@@ -272,7 +236,7 @@ def run_sweep():
             rows.append({"cms": [m, k], "n": n, "auto_ms": timed(g, 4 * m * k, 0), "direct_ms": timed(g, 4 * m * k, 1),
                          "lds_ms": timed(g, 4 * m * k, 2)})
     for r in rows:
-        print(json.dumps(r), flush=True)
+        benchlib.line(r)
     ctx.close()
     return rows
 
@@ -290,16 +254,13 @@ def main():
         print("bench_sketch: fewer than 20 timed calls: the medians are not for the record", file=sys.stderr)
     cpu = None
     if not args.no_cpu:
-        cpu = build_cpu_sketch()
+        cpu = cpu_lib()
         check_cpu_sketch(cpu)
     results = [run_shape(name, args, cpu) for name in args.shapes.split(",")]
     out = {"metric": "HyperLogLog add and Count-Min Sketch insert on the device", "shapes": results}
     if args.sweep:
         out["tier_sweep"] = run_sweep()
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        json.dump(out, f, indent=1)
-        f.write("\n")
+    benchlib.write(out, args.out)
 
 
 if __name__ == "__main__":

@@ -28,33 +28,24 @@ tests/memtable_ref.flush_closed on a small ragged log first.
 """
 import argparse
 import ctypes
-import json
 import os
-import subprocess
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 import numpy as np  # noqa: E402
 
+import benchlib  # noqa: E402
+
 SHAPES = {"a": (1 << 20, 100, "random16"), "b": (1 << 18, 4096, "random16"), "c": (1 << 20, 100, "user"),
           "bs": (1 << 18, 4096, "random16-sorted")}
 OVERWRITE = 0.25
 
 
-def build_cpu_sort():
-    src = os.path.join(ROOT, "tools", "cpu_sort.cpp")
-    so = os.path.join(ROOT, "build", "cpu_sort.so")
-    if not os.path.exists(so) or os.path.getmtime(so) < os.path.getmtime(src):
-        os.makedirs(os.path.dirname(so), exist_ok=True)
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", src, "-o", so])
-    lib = ctypes.CDLL(so)
-    lib.cpu_sort.restype = ctypes.c_double
-    lib.cpu_sort.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p,
-                             ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
-    return lib
+def cpu_lib():
+    vp, u64, pu64 = ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)
+    return benchlib.build_cpu("sort", {"cpu_sort": (ctypes.c_double, [vp, u64, u64, vp, vp, pu64, pu64])})
 
 
 def check_cpu_sort(cpu):
@@ -114,20 +105,12 @@ def run_shape(name, args, cpu):
     n, vs, kind = SHAPES[name]
     vs = args.value_bytes if args.value_bytes is not None else vs
     rng = np.random.default_rng(0x736F7274 + ord(name[0]))
-    L = _lib.lib()
-    ctx = _lib.Context(0)
-    s = torch.cuda.current_stream()
-    ctx.set_stream(s.cuda_stream)
+    L, ctx, s = benchlib.open_ctx()
     keys = make_keys(rng, n, kind)
     ks = keys.shape[1]
     rb = 30 + ks + vs
     total = n * rb
-    d_log = torch.empty(total, dtype=torch.uint8, device="cuda")
-    _lib.check(L.nkv_fill_splitmix64_dev(ctx.h, d_log.data_ptr(), total, 0x6E616B65))
-    v = d_log.view(n, rb)
-    v[:, 14:22] = torch.from_numpy(np.frombuffer(np.uint64(ks).tobytes(), np.uint8).copy()).cuda()
-    v[:, 22:30] = torch.from_numpy(np.frombuffer(np.uint64(vs).tobytes(), np.uint8).copy()).cuda()
-    v[:, 30:30 + ks] = torch.from_numpy(keys).cuda()
+    d_log = benchlib.device_log(ctx, n, ks, vs, keys)
     d_roff = torch.arange(n, dtype=torch.int64, device="cuda") * rb
     d_out = torch.empty(total, dtype=torch.uint8, device="cuda")
     d_off = torch.empty(8 * n, dtype=torch.uint8, device="cuda")
@@ -154,56 +137,20 @@ def run_shape(name, args, cpu):
     if not np.array_equal(got.reshape(no, rb), host_log.reshape(n, rb)[want.astype(np.int64)]):
         raise SystemExit(f"bench_sort: shape {name}: output bytes differ from the records at the host's sources")
 
-    for _ in range(args.warmup):
-        call()
-    ctx.set_timing(True)
-    call_ms, prep_ms, copy_ms = [], [], []
-    for _ in range(args.steps):
-        t0 = time.perf_counter()
-        call()
-        call_ms.append((time.perf_counter() - t0) * 1e3)
-        a, b = ctx.last_timing()
-        prep_ms.append(a)
-        copy_ms.append(b)
-    ctx.set_timing(False)
-
+    call_ms, prep_ms, copy_ms = benchlib.phase_ms(ctx, call, args.warmup, args.steps)
     # the comparator: hipMemcpyDtoDAsync of out_len bytes on the same stream
-    hip = ctypes.CDLL("libamdhip64.so.7")
-    hip.hipMemcpyDtoDAsync.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
     d_cmp = torch.empty(nb, dtype=torch.uint8, device="cuda")
-    memcpy_ms = []
-    for it in range(args.warmup + args.steps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(s)
-        rc = hip.hipMemcpyDtoDAsync(d_cmp.data_ptr(), d_out.data_ptr(), nb, s.cuda_stream)
-        e1.record(s)
-        torch.cuda.synchronize()
-        if rc != 0:
-            raise RuntimeError(f"hipMemcpyDtoDAsync -> {rc}")
-        if it >= args.warmup:
-            memcpy_ms.append(e0.elapsed_time(e1))
+    memcpy_ms = benchlib.memcpy_ms(s, d_cmp, d_out, nb, args.warmup, args.steps)
 
-    med = lambda x: float(np.median(x))  # noqa: E731
-    copy_gbs = 2 * nb / (med(copy_ms) * 1e-3) / 1e9
-    memcpy_gbs = 2 * nb / (med(memcpy_ms) * 1e-3) / 1e9
     out = {"shape": name, "records": n, "key_bytes": ks, "value_bytes": vs, "keys": kind, "log_len": total,
-           "n_out": no, "out_len": nb, "steps": args.steps, "warmup": args.warmup,
-           "call_ms": round(med(call_ms), 3), "prepare_ms": round(med(prep_ms), 3),
-           "copy_ms": round(med(copy_ms), 3), "copy_gbs": round(copy_gbs, 1),
-           "memcpy_ms": round(med(memcpy_ms), 3), "memcpy_gbs": round(memcpy_gbs, 1),
-           "copy_vs_memcpy": round(copy_gbs / memcpy_gbs, 3),
-           "call_ms_min_max": [round(min(call_ms), 3), round(max(call_ms), 3)],
-           "prepare_ms_min_max": [round(min(prep_ms), 3), round(max(prep_ms), 3)],
-           "copy_ms_min_max": [round(min(copy_ms), 3), round(max(copy_ms), 3)],
-           "memcpy_ms_min_max": [round(min(memcpy_ms), 3), round(max(memcpy_ms), 3)],
-           "verified_vs_host_sort": True}
-    try:  # the shader clock the box reports right after the timed loops (read only)
-        import re
-        smi = subprocess.run(["rocm-smi", "--showclocks"], capture_output=True, text=True, timeout=30).stdout
-        m = re.search(r"sclk.*?\((\d+)Mhz\)", smi)
-        out["sclk_mhz_after"] = int(m.group(1)) if m else None
-    except Exception:
-        out["sclk_mhz_after"] = None
+           "n_out": no, "out_len": nb, "steps": args.steps, "warmup": args.warmup}
+    call_med = benchlib.put(out, "call_ms", call_ms, 3)
+    benchlib.put(out, "prepare_ms", prep_ms, 3)
+    copy_gbs = 2 * nb / (benchlib.put(out, "copy_ms", copy_ms, 3) * 1e-3) / 1e9
+    memcpy_gbs = 2 * nb / (benchlib.put(out, "memcpy_ms", memcpy_ms, 3) * 1e-3) / 1e9
+    out.update({"copy_gbs": round(copy_gbs, 1), "memcpy_gbs": round(memcpy_gbs, 1),
+                "copy_vs_memcpy": round(copy_gbs / memcpy_gbs, 3), "verified_vs_host_sort": True,
+                "sclk_mhz_after": benchlib.sclk()})  # right after the timed loops
 
     if cpu is not None:
         h_out = np.empty(total, np.uint8)
@@ -211,8 +158,8 @@ def run_shape(name, args, cpu):
         secs = cpu.cpu_sort(host_log.ctypes.data, total, n, h_out.ctypes.data, None, ctypes.byref(a), ctypes.byref(b))
         out["cpu_sort_s"] = round(secs, 3)
         out["cpu_sort_agrees"] = bool((a.value, b.value) == (no, nb) and np.array_equal(h_out[:nb], got))
-        out["call_speedup_vs_cpu"] = round(secs * 1e3 / med(call_ms), 1)
-    print(json.dumps(out), flush=True)
+        out["call_speedup_vs_cpu"] = round(secs * 1e3 / call_med, 1)
+    benchlib.line(out)
     ctx.close()
     del d_log, d_out, d_cmp
     torch.cuda.empty_cache()
@@ -230,7 +177,7 @@ def main():
     args = ap.parse_args()
     cpu = None
     if not args.no_cpu:
-        cpu = build_cpu_sort()
+        cpu = cpu_lib()
         check_cpu_sort(cpu)
     results = [run_shape(name, args, cpu) for name in args.shapes.split(",")]
     by = {r["shape"]: r for r in results}
@@ -239,10 +186,7 @@ def main():
         out["prepare_c_over_a"] = round(by["c"]["prepare_ms"] / by["a"]["prepare_ms"], 2)
     if "a" in by and "cpu_sort_s" in by["a"]:
         out["device_beats_cpu_on_a"] = bool(by["a"]["call_ms"] < by["a"]["cpu_sort_s"] * 1e3)
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        json.dump(out, f, indent=1)
-        f.write("\n")
+    benchlib.write(out, args.out)
 
 
 if __name__ == "__main__":

@@ -4,13 +4,9 @@
 // into the log.  One pass sums the sizes into the record offsets; the records
 // are then encoded by `threads` threads over equal index ranges.  Same output as
 // nkv_encode_records.  Built by the tool with g++ -O2 -shared -pthread -lz.
-#include <stdint.h>
-#include <string.h>
 #include <zlib.h>
 
-#include <chrono>
-#include <thread>
-#include <vector>
+#include "cpu_common.hpp"
 
 namespace {
 
@@ -26,11 +22,11 @@ extern "C" double cpu_encode(const uint8_t* keys, const uint64_t* koff, const ui
                              const uint64_t* voff, const uint64_t* vlen, const int64_t* ts, int64_t ts_all,
                              const uint8_t* status, const uint8_t* type, uint64_t n, int threads, uint8_t* out,
                              uint64_t* out_len) {
-    const auto t0 = std::chrono::steady_clock::now();
+    const auto t0 = cpu::Clock::now();
     std::vector<uint64_t> off(n + 1);
     off[0] = 0;
     for (uint64_t i = 0; i < n; ++i) off[i + 1] = off[i] + 30 + klen[i] + vlen[i];
-    const auto work = [&](uint64_t lo, uint64_t hi) {
+    cpu::parallel_ranges(threads, n, [&](int, uint64_t lo, uint64_t hi) {
         for (uint64_t i = lo; i < hi; ++i) {
             const uint8_t *k = keys + koff[i], *v = vals + voff[i];
             uint8_t* r = out + off[i];
@@ -47,14 +43,7 @@ extern "C" double cpu_encode(const uint8_t* keys, const uint64_t* koff, const ui
             memcpy(r + 30, k, klen[i]);
             memcpy(r + 30 + klen[i], v, vlen[i]);
         }
-    };
-    if (threads <= 1) {
-        work(0, n);
-    } else {
-        std::vector<std::thread> pool;
-        for (int t = 0; t < threads; ++t) pool.emplace_back(work, n * t / threads, n * (t + 1) / threads);
-        for (auto& th : pool) th.join();
-    }
+    });
     *out_len = off[n];
-    return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    return cpu::since(t0);
 }

@@ -5,18 +5,12 @@
 // writers; this one has no file or buffer layer, so it is the faster of the two
 // shapes).  Same inputs and bytes as nkv_index_summary_dev.  Built by the tool
 // with g++ -O2 -shared.
-#include <stdint.h>
-#include <string.h>
-
-#include <chrono>
+#include "cpu_common.hpp"
 
 namespace {
 
-inline uint64_t le64(const uint8_t* p) {
-    uint64_t v;
-    memcpy(&v, p, 8);
-    return v;
-}
+using cpu::le64;
+
 inline uint8_t* put_entry(uint8_t* w, uint64_t ks, uint64_t off, const uint8_t* key) {
     memcpy(w, &ks, 8);
     memcpy(w + 8, &off, 8);
@@ -30,7 +24,7 @@ inline uint8_t* put_entry(uint8_t* w, uint64_t ks, uint64_t off, const uint8_t* 
 // (the tool sizes them from the device call's lengths); n >= 1, page >= 1.
 extern "C" double cpu_index(const uint8_t* stream, const uint64_t* rec_off, uint64_t n, uint64_t page,
                             uint8_t* index, uint8_t* summary, uint64_t* index_len, uint64_t* summary_len) {
-    const auto t0 = std::chrono::steady_clock::now();
+    const auto t0 = cpu::Clock::now();
     // the two header keys are known up front, so the entries go straight behind them
     const uint8_t *first = stream + rec_off[0], *last = stream + rec_off[n - 1];
     const uint64_t ks0 = le64(first + 14), ks1 = le64(last + 14);
@@ -52,5 +46,5 @@ extern "C" double cpu_index(const uint8_t* stream, const uint64_t* rec_off, uint
     memcpy(summary + 24 + ks0, last + 30, ks1);
     *index_len = uint64_t(wi - index);
     *summary_len = uint64_t(ws - summary);
-    return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    return cpu::since(t0);
 }

@@ -11,40 +11,23 @@
 // on `threads` threads.  Filters are not consulted: a filter only prunes, so
 // the hits are the device's.  hit[i] = (table << 32) | entry index, UINT64_MAX
 // if no table holds key i; data_off[i] the entry's stored Offset, else -1.
-#include <stdint.h>
-#include <string.h>
-
 #include <algorithm>
-#include <chrono>
-#include <thread>
-#include <vector>
+
+#include "cpu_common.hpp"
 
 namespace {
 
-struct Key {
-    const uint8_t* p;
-    uint64_t len;
-};
-
-inline int cmp(const Key& a, const Key& b) {
-    const int c = memcmp(a.p, b.p, size_t(std::min(a.len, b.len)));
-    if (c) return c < 0 ? -1 : 1;
-    return a.len < b.len ? -1 : (a.len > b.len ? 1 : 0);
-}
-
-inline Key key_of(const uint8_t* index, uint64_t off) {
-    uint64_t ks;
-    memcpy(&ks, index + off, 8);
-    return Key{index + off + 16, ks};
-}
+using cpu::Key;
+inline int cmp(const Key& a, const Key& b) { return cpu::compare(a, b); }
+// an Index entry: KeySize | Offset | Key
+inline Key key_of(const uint8_t* index, uint64_t off) { return Key{index + off + 16, cpu::le64(index + off)}; }
 
 // the chain of img[0, len): offsets into out (nullable); entries met, or UINT64_MAX if it breaks
 uint64_t walk(const uint8_t* img, uint64_t len, uint64_t* out) {
     uint64_t pos = 0, c = 0;
     while (pos < len) {
         if (len - pos < 16) return UINT64_MAX;
-        uint64_t ks;
-        memcpy(&ks, img + pos, 8);
+        const uint64_t ks = cpu::le64(img + pos);
         if (ks > len - pos - 16) return UINT64_MAX;
         if (out) out[c] = pos;
         ++c;
@@ -57,20 +40,20 @@ uint64_t walk(const uint8_t* img, uint64_t len, uint64_t* out) {
 
 extern "C" double cpu_index_walk(const uint8_t* index, uint64_t index_len, const uint8_t* summary,
                                  uint64_t summary_len, uint64_t* ent_off, uint64_t* n_out, uint64_t* s_out) {
-    const auto t0 = std::chrono::steady_clock::now();
+    const auto t0 = cpu::Clock::now();
     uint64_t h[3] = {0, 0, 0};
     if (summary_len >= 24) memcpy(h, summary, 24);
     const uint64_t at = 24 + h[0] + h[1];
     *s_out = at + h[2] <= summary_len ? walk(summary + at, h[2], nullptr) : UINT64_MAX;
     *n_out = walk(index, index_len, ent_off);
-    return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    return cpu::since(t0);
 }
 
 extern "C" double cpu_locate(const uint8_t* const* indexes, const uint64_t* const* offs, const uint64_t* ns, int T,
                              const uint8_t* keys, const uint64_t* koff, const uint64_t* klen, uint64_t q,
                              uint64_t* hit, int64_t* data_off, int threads) {
-    const auto t0 = std::chrono::steady_clock::now();
-    auto work = [&](uint64_t lo, uint64_t hi) {
+    const auto t0 = cpu::Clock::now();
+    cpu::parallel_ranges(threads, q, [&](int, uint64_t lo, uint64_t hi) {
         for (uint64_t i = lo; i < hi; ++i) {
             const Key k{keys + koff[i], klen[i]};
             uint64_t h = UINT64_MAX;
@@ -88,9 +71,6 @@ extern "C" double cpu_locate(const uint8_t* const* indexes, const uint64_t* cons
             hit[i] = h;
             data_off[i] = h == UINT64_MAX ? -1 : d;
         }
-    };
-    std::vector<std::thread> pool;
-    for (int w = 0; w < threads; ++w) pool.emplace_back(work, q * w / threads, q * (w + 1) / threads);
-    for (auto& th : pool) th.join();
-    return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    });
+    return cpu::since(t0);
 }

@@ -6,41 +6,23 @@
 //
 // hit[i] = (table << 32) | record index, UINT64_MAX if no table holds key i.
 // Returns the wall-clock seconds of the search.
-#include <stdint.h>
-#include <string.h>
-
 #include <algorithm>
-#include <chrono>
-#include <numeric>
-#include <thread>
-#include <vector>
+
+#include "cpu_common.hpp"
 
 namespace {
 
-struct Key {
-    const uint8_t* p;
-    uint64_t len;
-};
-
-inline int cmp(const Key& a, const Key& b) {
-    const int c = memcmp(a.p, b.p, size_t(std::min(a.len, b.len)));
-    if (c) return c < 0 ? -1 : 1;
-    return a.len < b.len ? -1 : (a.len > b.len ? 1 : 0);
-}
-
-inline Key key_of(const uint8_t* stream, uint64_t off) {
-    uint64_t ks;
-    memcpy(&ks, stream + off + 14, 8);
-    return Key{stream + off + 30, ks};
-}
+using cpu::Key;
+inline int cmp(const Key& a, const Key& b) { return cpu::compare(a, b); }
+inline Key key_of(const uint8_t* stream, uint64_t off) { return cpu::record_key(stream + off); }
 
 }  // namespace
 
 extern "C" double cpu_lookup(const uint8_t* const* streams, const uint64_t* const* offs, const uint64_t* ns, int T,
                              const uint8_t* keys, const uint64_t* koff, const uint64_t* klen, uint64_t q,
                              uint64_t* hit, int threads) {
-    const auto t0 = std::chrono::steady_clock::now();
-    auto work = [&](uint64_t lo, uint64_t hi) {
+    const auto t0 = cpu::Clock::now();
+    cpu::parallel_ranges(threads, q, [&](int, uint64_t lo, uint64_t hi) {
         for (uint64_t i = lo; i < hi; ++i) {
             const Key k{keys + koff[i], klen[i]};
             uint64_t h = UINT64_MAX;
@@ -53,9 +35,6 @@ extern "C" double cpu_lookup(const uint8_t* const* streams, const uint64_t* cons
             }
             hit[i] = h;
         }
-    };
-    std::vector<std::thread> pool;
-    for (int w = 0; w < threads; ++w) pool.emplace_back(work, q * w / threads, q * (w + 1) / threads);
-    for (auto& th : pool) th.join();
-    return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    });
+    return cpu::since(t0);
 }

@@ -10,14 +10,10 @@
 // value per write, Count, memusage (the sizes of the first writes), and per
 // query the arrival index of the key's latest write or UINT64_MAX.  Built by
 // the tool with g++ -O2 -shared -pthread.
-#include <stdint.h>
-#include <string.h>
-
-#include <chrono>
 #include <string_view>
-#include <thread>
 #include <unordered_map>
-#include <vector>
+
+#include "cpu_common.hpp"
 
 namespace {
 
@@ -25,24 +21,11 @@ struct Span {
     uint32_t first, latest;
 };
 using Map = std::unordered_map<std::string_view, Span>;
+using cpu::since;
 
-inline uint64_t le64(const uint8_t* p) {
-    uint64_t v;
-    memcpy(&v, p, 8);
-    return v;
-}
 inline std::string_view key_at(const uint8_t* log, uint64_t off) {
-    return {reinterpret_cast<const char*>(log + off + 30), size_t(le64(log + off + 14))};
-}
-inline double since(std::chrono::steady_clock::time_point t0) {
-    return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-}
-template <class F>
-void run(int T, F f) {
-    if (T == 1) return f(0);
-    std::vector<std::thread> th;
-    for (int t = 0; t < T; ++t) th.emplace_back(f, t);
-    for (auto& x : th) x.join();
+    const cpu::Key k = cpu::record_key(log + off);
+    return {reinterpret_cast<const char*>(k.p), size_t(k.len)};
 }
 
 }  // namespace
@@ -57,12 +40,12 @@ extern "C" void cpu_memtable(const uint8_t* log, const uint64_t* off, uint64_t n
     std::vector<uint64_t> count(T, 0), mem(T, 0);
     std::vector<size_t> hash(T > 1 ? n : 0);
     const std::hash<std::string_view> H;
-    auto t0 = std::chrono::steady_clock::now();
+    auto t0 = cpu::Clock::now();
     if (T > 1)
-        run(T, [&](int t) {
-            for (uint64_t i = n * t / T; i < n * (t + 1) / T; ++i) hash[i] = H(key_at(log, off[i]));
+        cpu::parallel_ranges(T, n, [&](int, uint64_t lo, uint64_t hi) {
+            for (uint64_t i = lo; i < hi; ++i) hash[i] = H(key_at(log, off[i]));
         });
-    run(T, [&](int t) {
+    cpu::parallel_ranges(T, n, [&](int t, uint64_t, uint64_t) {  // every worker walks all the writes, for its shard
         Map& m = maps[t];
         m.reserve(n / T + 16);
         for (uint64_t i = 0; i < n; ++i) {
@@ -72,16 +55,16 @@ extern "C" void cpu_memtable(const uint8_t* log, const uint64_t* off, uint64_t n
             is_new[i] = fresh;
             if (fresh) {
                 ++count[t];
-                mem[t] += 30 + le64(log + off[i] + 14) + le64(log + off[i] + 22);
+                mem[t] += cpu::record_size(log + off[i]);
             }
         }
     });
     seconds[0] = since(t0);
     totals[0] = totals[1] = 0;
     for (int t = 0; t < T; ++t) totals[0] += count[t], totals[1] += mem[t];
-    t0 = std::chrono::steady_clock::now();
-    run(T, [&](int t) {
-        for (uint64_t i = q * t / T; i < q * (t + 1) / T; ++i) {
+    t0 = cpu::Clock::now();
+    cpu::parallel_ranges(T, q, [&](int, uint64_t lo, uint64_t hi) {
+        for (uint64_t i = lo; i < hi; ++i) {
             const std::string_view k{reinterpret_cast<const char*>(keys + koff[i]), size_t(klen[i])};
             const Map& m = maps[T > 1 ? H(k) % T : 0];
             const auto it = m.find(k);

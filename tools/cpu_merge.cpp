@@ -4,14 +4,13 @@
 // record where this uses a heap, so this is the faster of the two shapes).
 // Same semantics as nkv_merge_records: one record per key, newest Timestamp,
 // ties by (predecessor key, run).  Built by the tool with g++ -O2 -shared.
-#include <stdint.h>
-#include <string.h>
-
-#include <chrono>
 #include <queue>
-#include <vector>
+
+#include "cpu_common.hpp"
 
 namespace {
+
+using cpu::le64;
 
 struct Head {
     const uint8_t* rec;   // the record
@@ -19,16 +18,9 @@ struct Head {
     int run;
 };
 
-inline uint64_t le64(const uint8_t* p) {
-    uint64_t v;
-    memcpy(&v, p, 8);
-    return v;
-}
 inline int cmp_key(const uint8_t* a, const uint8_t* b) {  // a null record sorts first ("no predecessor")
     if (!a || !b) return (a ? 1 : 0) - (b ? 1 : 0);
-    const uint64_t la = le64(a + 14), lb = le64(b + 14);
-    const int c = memcmp(a + 30, b + 30, la < lb ? la : lb);
-    return c ? c : (la < lb ? -1 : (la > lb ? 1 : 0));
+    return cpu::compare(cpu::record_key(a), cpu::record_key(b));
 }
 // true if a comes out after b
 struct After {
@@ -48,7 +40,7 @@ struct After {
 // Returns the seconds the merge took; *n_out / *out_len as nkv_merge_records.
 extern "C" double cpu_merge(const uint8_t* const* streams, const uint64_t* stream_len, int k, uint8_t* out,
                             uint64_t* n_out, uint64_t* out_len) {
-    const auto t0 = std::chrono::steady_clock::now();
+    const auto t0 = cpu::Clock::now();
     std::priority_queue<Head, std::vector<Head>, After> pq;
     std::vector<const uint8_t*> end(k);
     for (int r = 0; r < k; ++r) {
@@ -60,7 +52,7 @@ extern "C" double cpu_merge(const uint8_t* const* streams, const uint64_t* strea
     while (!pq.empty()) {
         const Head h = pq.top();
         pq.pop();
-        const uint64_t size = 30 + le64(h.rec + 14) + le64(h.rec + 22);
+        const uint64_t size = cpu::record_size(h.rec);
         if (!last || cmp_key(last, h.rec) != 0) {  // the first of its key wins
             memcpy(out + at, h.rec, size);
             last = out + at;
@@ -71,5 +63,5 @@ extern "C" double cpu_merge(const uint8_t* const* streams, const uint64_t* strea
     }
     *n_out = n;
     *out_len = at;
-    return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    return cpu::since(t0);
 }

@@ -2,13 +2,9 @@
 // of MurmurHash3_x86_32 plus the sketch update (ds/hll/hll.go:43-62,
 // ds/cmsketch/cmsketch.go:76-87), on one thread or on several with per-thread
 // copies that are merged at the end.  Built by the tool with g++ -O2.
-#include <stdint.h>
-#include <string.h>
-
 #include <algorithm>
-#include <chrono>
-#include <thread>
-#include <vector>
+
+#include "cpu_common.hpp"
 
 namespace {
 
@@ -49,22 +45,6 @@ uint32_t murmur3_32(const uint8_t* data, uint64_t len, uint32_t seed) {
     return h;
 }
 
-template <class F>
-void split(uint64_t n, int threads, F body) {
-    if (threads <= 1) {
-        body(0, uint64_t(0), n);
-        return;
-    }
-    std::vector<std::thread> pool;
-    for (int t = 0; t < threads; ++t)
-        pool.emplace_back(body, t, n * uint64_t(t) / threads, n * uint64_t(t + 1) / threads);
-    for (auto& th : pool) th.join();
-}
-
-double since(std::chrono::steady_clock::time_point t0) {
-    return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-}
-
 }  // namespace
 
 // reg (2^p bytes) is max-ed in place; returns the seconds of the loop and the merge
@@ -73,8 +53,8 @@ extern "C" double cpu_hll(const uint8_t* base, const uint64_t* off, const uint64
     const uint64_t M = uint64_t(1) << p;
     threads = std::max(threads, 1);
     std::vector<std::vector<uint8_t>> part(threads, std::vector<uint8_t>(M, 0));
-    const auto t0 = std::chrono::steady_clock::now();
-    split(n, threads, [&](int t, uint64_t lo, uint64_t hi) {
+    const auto t0 = cpu::Clock::now();
+    cpu::parallel_ranges(threads, n, [&](int t, uint64_t lo, uint64_t hi) {
         uint8_t* r = part[t].data();
         for (uint64_t i = lo; i < hi; ++i) {
             const uint32_t h = murmur3_32(base + off[i], len[i], 0);
@@ -85,7 +65,7 @@ extern "C" double cpu_hll(const uint8_t* base, const uint64_t* off, const uint64
     });
     for (int t = 0; t < threads; ++t)
         for (uint64_t j = 0; j < M; ++j) reg[j] = std::max(reg[j], part[t][j]);
-    return since(t0);
+    return cpu::since(t0);
 }
 
 // table (k rows of m counters) is added to in place
@@ -94,13 +74,13 @@ extern "C" double cpu_cms(const uint8_t* base, const uint64_t* off, const uint64
     const uint64_t T = uint64_t(m) * k;
     threads = std::max(threads, 1);
     std::vector<std::vector<uint32_t>> part(threads, std::vector<uint32_t>(T, 0));
-    const auto t0 = std::chrono::steady_clock::now();
-    split(n, threads, [&](int t, uint64_t lo, uint64_t hi) {
+    const auto t0 = cpu::Clock::now();
+    cpu::parallel_ranges(threads, n, [&](int t, uint64_t lo, uint64_t hi) {
         uint32_t* c = part[t].data();
         for (uint64_t i = lo; i < hi; ++i)
             for (uint32_t j = 0; j < k; ++j) c[uint64_t(j) * m + murmur3_32(base + off[i], len[i], seed0 + j) % m] += 1;
     });
     for (int t = 0; t < threads; ++t)
         for (uint64_t j = 0; j < T; ++j) table[j] += part[t][j];
-    return since(t0);
+    return cpu::since(t0);
 }

@@ -5,25 +5,13 @@
 // order, and one pass keeps the last record of each group of equal keys and
 // copies it.  Same semantics as nkv_sort_records.  Built by the tool with
 // g++ -O2 -shared.
-#include <stdint.h>
-#include <string.h>
-
 #include <algorithm>
-#include <chrono>
-#include <vector>
+
+#include "cpu_common.hpp"
 
 namespace {
 
-inline uint64_t le64(const uint8_t* p) {
-    uint64_t v;
-    memcpy(&v, p, 8);
-    return v;
-}
-inline int cmp_key(const uint8_t* a, const uint8_t* b) {
-    const uint64_t la = le64(a + 14), lb = le64(b + 14);
-    const int c = memcmp(a + 30, b + 30, la < lb ? la : lb);
-    return c ? c : (la < lb ? -1 : (la > lb ? 1 : 0));
-}
+inline int cmp_key(const uint8_t* a, const uint8_t* b) { return cpu::compare(cpu::record_key(a), cpu::record_key(b)); }
 
 }  // namespace
 
@@ -31,12 +19,12 @@ inline int cmp_key(const uint8_t* a, const uint8_t* b) {
 // src (nullable, n entries): the arrival index of every output record.
 extern "C" double cpu_sort(const uint8_t* log, uint64_t log_len, uint64_t n, uint8_t* out, uint64_t* src,
                            uint64_t* n_out, uint64_t* out_len) {
-    const auto t0 = std::chrono::steady_clock::now();
+    const auto t0 = cpu::Clock::now();
     std::vector<const uint8_t*> rec(n);
     uint64_t at = 0;
     for (uint64_t i = 0; i < n && at + 30 <= log_len; ++i) {
         rec[i] = log + at;
-        at += 30 + le64(log + at + 14) + le64(log + at + 22);
+        at += cpu::record_size(log + at);
     }
     std::vector<uint32_t> order(n);
     for (uint64_t i = 0; i < n; ++i) order[i] = uint32_t(i);
@@ -47,7 +35,7 @@ extern "C" double cpu_sort(const uint8_t* log, uint64_t log_len, uint64_t n, uin
     for (uint64_t s = 0; s < n; ++s) {
         if (s + 1 < n && cmp_key(rec[order[s]], rec[order[s + 1]]) == 0) continue;  // shadowed by a later write
         const uint8_t* r = rec[order[s]];
-        const uint64_t size = 30 + le64(r + 14) + le64(r + 22);
+        const uint64_t size = cpu::record_size(r);
         memcpy(out + at, r, size);
         if (src) src[m] = order[s];
         at += size;
@@ -55,5 +43,5 @@ extern "C" double cpu_sort(const uint8_t* log, uint64_t log_len, uint64_t n, uin
     }
     *n_out = m;
     *out_len = at;
-    return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    return cpu::since(t0);
 }
