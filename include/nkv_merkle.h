@@ -55,6 +55,10 @@
  *     over a Data file      core/lsmtree/lsmtree.go:137-231     nkv_frame_records
  *   wal.readEntireSegment   core/wal/wal.go:293-328             nkv_frame_records[_dev] with
  *     (ReadAllSegments, ReadSegmentsInRange, ...)                 segment offsets
+ *   CoreEngine.IsLegal,     engine/coreeng/coreeng.go:47-59,    nkv_admit_dev
+ *     getTokenBucket,         63-75, 165-199, 223-234
+ *     HasEnoughTokens,      ds/tokenbucket/tokenbucket.go:51-83
+ *     ToBytes / FromBytes
  *
  * Conventions
  *   - Every function returns an nkv_status (0 = NKV_OK) unless noted; nothing
@@ -82,7 +86,7 @@
  *         d_summary of nkv_index_summary_dev, d_status and d_stage of
  *         nkv_lookup_dev and nkv_locate_dev, d_out of nkv_lookup_values_dev, d_out of
  *         nkv_encode_records_dev, d_is_new of nkv_memtable_add_dev, d_status of
- *         nkv_memtable_find_dev;
+ *         nkv_memtable_find_dev, d_verdict and d_last of nkv_admit_dev;
  *       digest arrays (d_nodes, nkv_table.nodes, d_roots and d_out entries of
  *         the group calls), 4-byte aligned: level starts inside a nodes buffer
  *         are multiples of 20 bytes, no more;
@@ -92,7 +96,8 @@
  *       uint64_t arrays (d_rec_off, the frame's included, d_voff, d_vlen, d_stats,
  *         d_out_off, the encode's d_out_off included, d_out_src, d_hit,
  *         d_seg_first, d_seg_len, the memtable's d_state and d_index, d_ent_off,
- *         d_data_off), 8-byte aligned.
+ *         d_data_off, and d_bucket, d_wait and d_group of nkv_admit_dev), 8-byte
+ *         aligned.
  *     nkv_leaf_hash*_dev write level 0 only (20 n bytes); nkv_tree_reduce_dev
  *     leaves level 0 as given; d_bits is ((m + 31) / 32) * 4 bytes; the merge
  *     and the sort write out_len bytes and n_out entries; nkv_index_summary_dev writes
@@ -110,7 +115,10 @@
  *     overlay only those of the keys the memtable holds); nkv_index_open_dev
  *     writes *n_out entries of d_ent_off, and none for a refused pair;
  *     nkv_locate_dev writes q entries of d_hit, d_data_off and d_status (with
- *     overlay only those whose status was ABSENT) and q T bytes of d_stage.
+ *     overlay only those whose status was ABSENT) and q T bytes of d_stage;
+ *     nkv_admit_dev writes n bytes of d_verdict and of d_last, 32 n bytes of
+ *     d_bucket and n entries of d_wait and d_group, and none of them when its
+ *     verdict word is nonzero.
  *     Inputs are never
  *     written: values, record streams, offset and length arrays, segment offsets, the merge's
  *     runs, the sort's log, the lookup's tables, filters and query keys, the
@@ -1131,6 +1139,98 @@ int nkv_memtable_find_dev(nkv_ctx *ctx, const void *d_log, uint64_t log_len, con
                           uint64_t n, const void *d_index, uint64_t slots, const void *d_keys,
                           const uint64_t *d_koff, const uint64_t *d_klen, uint64_t q, uint32_t table_id,
                           int overlay, uint64_t *d_hit, uint8_t *d_status, uint32_t *d_err);
+
+/* ---- engine admission (engine/coreeng/coreeng.go:47-75, 165-199, 223-234
+ *      over ds/tokenbucket/tokenbucket.go:51-83) ----
+ * The step CoreEngine.Put, Get and Delete run first, for a batch of n requests
+ * (user, key, now) in arrival order: IsLegal(key) -- a key whose first
+ * start_len bytes equal conf.InternalStart is refused before any bucket is
+ * read, so it is not part of its user's sequence -- then the user's token
+ * bucket, getTokenBucket -> HasEnoughTokens.  A bucket is (MaxTokens, Tokens,
+ * Timestamp, ResetInterval), four int64; ToBytes writes them as four
+ * little-endian u64 in that order, 32 bytes.  HasEnoughTokens at time now: if
+ * now - Timestamp > ResetInterval then Timestamp = now, Tokens = MaxTokens - 1,
+ * allow; else if Tokens > 0 then Tokens--, allow; else deny with the state
+ * unchanged.  The engine puts the bucket record (key InternalStart ++ user,
+ * Value = the image) for every allowed request and nothing for a denied one.
+ * Every time.Now().Unix() of one request is the one caller-supplied now_i
+ * here.  tests/admit_ref.py restates all of it statement by statement.
+ *
+ * Requests: user i is the ulen[i] bytes at users + uoff[i] (any alignment, the
+ * empty user and repeated or overlapping spans allowed), key i likewise; with
+ * koff NULL there is no IsLegal step and every request is legal.  ts holds n
+ * times, or is NULL and ts_all is the time of all (as nkv_puts).  Times must be
+ * non-decreasing over the whole batch, not only within a user: that is what
+ * makes a user's windows well defined, and with the range below it keeps
+ * now - Timestamp from wrapping.  Stored buckets (buckets, boff and bstatus
+ * NULL together = every bucket fresh): bstatus[i] is a status byte as
+ * nkv_lookup_dev / nkv_memtable_find_dev write it, NKV_GET_LIVE meaning "the 32
+ * bytes at buckets + boff[i] (any alignment) are user i's stored bucket",
+ * anything else a fresh bucket tokenbucket.New(max_tokens, reset_interval) at
+ * that request's time.  A caller looks InternalStart ++ user up for all n
+ * requests (duplicates are fine there) and hands the answers over unchanged:
+ * only the entry of a user's first legal request is read; the others, and
+ * boff where bstatus is not LIVE, are ignored.  A stored bucket brings its own
+ * MaxTokens and ResetInterval (FromBytes), not the call's.  uoff, ulen, koff,
+ * klen, ts and boff are 8-byte aligned.
+ *
+ * Outputs, by request (all but d_verdict nullable):
+ *   d_verdict  n bytes at any address: NKV_ADMIT_ILLEGAL, _ALLOWED, _THROTTLED.
+ *   d_bucket   32 n bytes, 8-byte aligned: the ToBytes image after the request;
+ *              for an allowed one the Value of the bucket record the engine
+ *              puts, for a throttled one the unchanged state, for an illegal
+ *              one zeros.
+ *   d_wait     n int64: the "seconds to go" a throttled request prints,
+ *              ResetInterval - (now - Timestamp); 0 otherwise.
+ *   d_group    n uint64: the arrival index of the first legal request of the
+ *              same user, UINT64_MAX for an illegal one.  Its fixed points are
+ *              the distinct users.
+ *   d_last     n bytes at any address: 1 iff the request is its user's last
+ *              legal one in the batch; its d_bucket entry is then the user's
+ *              final state, what the next batch finds stored.
+ * The answers are those of the n requests served one after the other.
+ * Asynchronous on the context's stream; scratch comes from the context.
+ *
+ * NKV_ERR_INVALID, with nothing launched: a null context, req or start; n >
+ * 2^31 - 1; start_len outside 1..64 (coreconf.validate refuses the empty
+ * string); max_tokens or reset_interval outside 1..2^62 - 1; users NULL with
+ * users_len > 0, and the same for keys; koff given without klen; buckets, boff
+ * and bstatus not NULL together; with n > 0 a null uoff, ulen or d_verdict.
+ * n = 0 returns NKV_OK and writes nothing.  Device-side verdicts go to d_err
+ * (nullable, one uint32_t, need not be initialised; with d_err NULL the call
+ * synchronizes and returns NKV_ERR_INVALID instead).  When the word is nonzero
+ * no byte of any output has been written:
+ *   bit 0  a user's or a key's span outside its blob (a wrapped off + len is
+ *          caught);
+ *   bit 1  a key shorter than start, where the reference indexes out of range;
+ *   bit 2  a time that is negative, above 2^62 - 1, or smaller than the time of
+ *          the request before it;
+ *   bit 3  a stored bucket that is read and has MaxTokens or ResetInterval
+ *          outside 1..2^62 - 1 or a Timestamp outside 0..2^62 - 1.  Tokens may
+ *          be any int64, and a Timestamp may lie in the future.
+ * Under NKV_TIMING_EVENTS the "leaf" interval is the validation, the grouping
+ * and the sort, the "reduce" interval the windows, the ranks and the scatter. */
+#define NKV_ADMIT_ILLEGAL 0
+#define NKV_ADMIT_ALLOWED 1
+#define NKV_ADMIT_THROTTLED 2
+#define NKV_ADMIT_BAD_SPAN 1
+#define NKV_ADMIT_BAD_KEY 2
+#define NKV_ADMIT_BAD_TIME 4
+#define NKV_ADMIT_BAD_BUCKET 8
+typedef struct nkv_requests {  /* pointers on the context's device */
+    const void *users;     uint64_t users_len; /* user i = users[uoff[i] .. uoff[i] + ulen[i]) */
+    const uint64_t *uoff;  const uint64_t *ulen;
+    const void *keys;      uint64_t keys_len;  /* key i  = keys[koff[i] .. koff[i] + klen[i]) */
+    const uint64_t *koff;  const uint64_t *klen; /* koff NULL: no IsLegal step */
+    const int64_t *ts;     /* n times, or NULL: ts_all for every request */
+    int64_t ts_all;
+    const void *buckets;   /* stored buckets: 32 bytes at buckets + boff[i] where bstatus[i] is NKV_GET_LIVE */
+    const uint64_t *boff;  const uint8_t *bstatus;
+    uint64_t n;
+} nkv_requests;
+int nkv_admit_dev(nkv_ctx *ctx, const nkv_requests *req, const void *start, uint64_t start_len,
+                  int64_t max_tokens, int64_t reset_interval, uint8_t *d_verdict, void *d_bucket,
+                  int64_t *d_wait, uint64_t *d_group, uint8_t *d_last, uint32_t *d_err);
 
 /* ---- several tables per call (compaction's runs, consecutive flushes) ----
  * One table of device-resident leaves, described for nkv_trees_dev /

@@ -112,6 +112,22 @@ class NkvPuts(ctypes.Structure):
                 ("n", _u64)]
 
 
+class NkvRequests(ctypes.Structure):
+    """struct nkv_requests: a batch of (user, key, now) requests for nkv_admit_dev
+    (koff None = no IsLegal step; ts None = ts_all; buckets / boff / bstatus None together = fresh buckets)."""
+    _fields_ = [("users", _vp), ("users_len", _u64), ("uoff", _vp), ("ulen", _vp), ("keys", _vp), ("keys_len", _u64),
+                ("koff", _vp), ("klen", _vp), ("ts", _vp), ("ts_all", ctypes.c_int64), ("buckets", _vp),
+                ("boff", _vp), ("bstatus", _vp), ("n", _u64)]
+
+
+NKV_ADMIT_ILLEGAL = 0
+NKV_ADMIT_ALLOWED = 1
+NKV_ADMIT_THROTTLED = 2
+NKV_ADMIT_BAD_SPAN = 1
+NKV_ADMIT_BAD_KEY = 2
+NKV_ADMIT_BAD_TIME = 4
+NKV_ADMIT_BAD_BUCKET = 8
+ADMIT_VERDICTS = {1: "BAD_SPAN", 2: "BAD_KEY", 4: "BAD_TIME", 8: "BAD_BUCKET"}
 NKV_MERGE_MAX_RUNS = 16
 NKV_LOOKUP_MAX_TABLES = 32
 NKV_STAGE_NOT_SEARCHED = 0
@@ -234,6 +250,8 @@ SIGNATURES = {
     "nkv_memtable_add_dev": (_int, [_vp, _vp, _u64, _vp, _u64, _u64, _vp, _u64, _int, _u64, _u64, _vp, _vp, _vp]),
     "nkv_memtable_find_dev": (_int, [_vp, _vp, _u64, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _u64, _u32, _int, _vp,
                                      _vp, _vp]),
+    "nkv_admit_dev": (_int, [_vp, ctypes.POINTER(NkvRequests), _vp, _u64, ctypes.c_int64, ctypes.c_int64, _vp, _vp,
+                             _vp, _vp, _vp, _vp]),
     "nkv_ctx_clock": (_int, [_vp, ctypes.POINTER(ctypes.c_double), _u64p]),
     "nkv_ctx_last_host_timing": (_int, [_vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float),
                                         ctypes.POINTER(ctypes.c_float)]),

@@ -20,11 +20,11 @@ CSRC = os.path.join(PKG, "csrc")
 SO = os.path.join(PKG, "libnkvmerkle.so")
 SOURCES = ["leaf.hip", "reduce.hip", "small_tree.hip", "plan.hip", "crc.hip", "bloom.hip", "merge.hip",
            "memtable.hip", "memindex.hip", "index.hip", "lookup.hip", "locate.hip", "encode.hip", "sketch.hip", "frame.hip",
-           "context.cpp", "stage.cpp", "tree.cpp", "small_host.cpp",
+           "admit.hip", "context.cpp", "stage.cpp", "tree.cpp", "small_host.cpp",
            "group.cpp", "host_stage.cpp"]
 HEADERS = ["internal.hpp", "context.hpp", "sha1_dev.hpp", "sha1_feed_dev.hpp", "tree_dev.hpp", "host_stage.hpp",
            "crc_dev.hpp", "murmur_dev.hpp", "bytes_dev.hpp", "merge_copy_dev.hpp", "record_dev.hpp",
-           "search_dev.hpp"]
+           "search_dev.hpp", "admit_dev.hpp"]
 ARCH = os.environ.get("NKV_OFFLOAD_ARCH", "gfx950")
 FLAGS = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-shared", "-pthread",
          "-Wall", "-Wno-unused-result"]
